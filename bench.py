@@ -46,6 +46,14 @@ barrier -> K steps -> barrier, max over ranks.  value = all nonces of all
 ranks / that time.  The answer is checked against the committed golden
 (tests/golden/) for the workload; a wrong answer exits non-zero.
 
+A plain run does only that: set-up, warmup, the timed steps, the line (and,
+with --dump-outputs DIR, DIR/result.npy: what the last timed step returned).
+Its roofline block is computed from the timed steps' own launch records and
+the committed PMC summary.  --full adds, after the timed steps, what takes
+runs of its own: the clock under the dominant kernel (measure_clock, so
+issue_bound.frac), the C4 step (c4), the one-process C4 child under torchrun
+(c4_one_process) and the CPU baselines (cpu_baseline).
+
 Also reported:
   roofline      the dominant launch, three ways:
                 frac       canonical: algorithmic int32 ops (nonces x C x
@@ -136,6 +144,20 @@ def golden(msg, lo, hi):
         if bytes.fromhex(c["msg_hex"]) == msg and c["lower"] == lo and c["upper"] == hi:
             return [c["hash"], c["nonce"]]
     return None
+
+
+def dump_outputs(outdir, res):
+    """--dump-outputs: what the last timed step's search returned, the pair
+    (hash, nonce) a caller of bm_search_gpu receives, as outdir/result.npy: a
+    float64 array of four 32-bit halves [hash >> 32, hash & 0xffffffff,
+    nonce >> 32, nonce & 0xffffffff], each exact in float64 (a 64-bit value
+    itself is not).  The workload of a config is fixed (workload()), so two
+    builds run with the same arguments are compared value for value."""
+    import numpy as np
+    h, n = int(res[0]), int(res[1])
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "result.npy"),
+            np.array([h >> 32, h & 0xFFFFFFFF, n >> 32, n & 0xFFFFFFFF], dtype=np.float64))
 
 
 def compressions_per_nonce(msg_len, digits):
@@ -997,7 +1019,17 @@ def main():
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N-way split on ONE GPU (all ranks / devices are GPU 0): exercises the multi-GPU "
                          "path on a one-GPU box; not a scaling measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything that takes runs of its own: the clock under the "
+                         "dominant kernel (--clock-seconds), the warm C4 step (--no-c4 drops it), at N > 1 under "
+                         "torchrun the one-process C4 child, and at N = 1 the CPU baselines (--no-cpu-baseline "
+                         "drops them).  Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step's search returned as "
+                         "DIR/result.npy (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline, args.no_c4, args.clock_seconds = True, True, 0.0
     if args.steps is None:
         args.steps = 2 if args.config == "C4" else 40
     if args.warmup is None:
@@ -1048,9 +1080,13 @@ def main():
     clocks = grp.gather(sysfs_clock) if world > 1 else [sysfs_clock]
     starts = grp.gather(t0_wall) if world > 1 else [t0_wall]
     # the clock under the dominant kernel on THIS box, for the issue bound
-    # (untimed, after the timed region; every rank on its own GPU)
+    # (untimed, after the timed region; every rank on its own GPU; --full only:
+    # it takes searches of its own)
     dom0 = doms[-1][0]
-    box_clock = measure_clock(dev, msg, dom0.digits, lo, hi, seconds=args.clock_seconds) if dom0 is not None else None
+    box_clock = (measure_clock(dev, msg, dom0.digits, lo, hi, seconds=args.clock_seconds)
+                 if args.full and dom0 is not None else None)
+    if args.dump_outputs and grp.rank == 0:
+        dump_outputs(args.dump_outputs, res)
     grp.barrier()
     # north_star's 2^40 target, measured at every N: one warm C4
     # step, after the clock measurement so that the issue bound's clock is

@@ -47,6 +47,20 @@ def test_workloads_and_goldens():
     assert bench.golden(b"bradfitz", 0, 12345) is None
 
 
+def test_dump_outputs_is_exact(tmp_path):
+    """--dump-outputs: result.npy holds the (hash, nonce) pair as four 32-bit
+    halves in float64, so 64-bit values that float64 cannot hold come back
+    exactly; the directory is created."""
+    import numpy as np
+    d = tmp_path / "a" / "b"
+    for h, n in ((2 ** 64 - 1, 2 ** 64 - 2), (2 ** 53 + 1, 0), (16555811, 890536971553)):
+        bench.dump_outputs(str(d), (h, n))
+        a = np.load(d / "result.npy")
+        assert a.dtype == np.float64 and a.shape == (4,)
+        assert ((int(a[0]) << 32) | int(a[1]), (int(a[2]) << 32) | int(a[3])) == (h, n)
+    assert sorted(p.name for p in d.iterdir()) == ["result.npy"]
+
+
 def test_multi_gpu_without_devices_fails_loudly():
     """--gpus 2 with no launcher and fewer than 2 visible devices exits 2 with
     a message (never a silent 1-GPU line); a WORLD_SIZE that disagrees with
@@ -520,7 +534,7 @@ def probe_child(args, n):
     others = [int(open(os.path.join(os.environ["PIDDIR"], f"pid.{r}")).read()) for r in range(1, 2)]
     return {"GHs": 2.0, "others_running": bench.wait_exited(others, timeout_s=0.0), "n": n}
 bench._c4_one_process_child = probe_child
-sys.argv = ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "3", "--no-cpu-baseline", "--clock-sample", "0"]
+sys.argv = ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "3", "--full", "--no-cpu-baseline", "--clock-sample", "0"]
 bench.main()
 """
 
@@ -553,3 +567,67 @@ def test_bench_main_world2_one_process_after_ranks_exit(oracle, tmp_path):
     assert line["rccl"]["version_str"] == "2.27.3" and line["scaling_valid"] is True
     one = line["c4_one_process"]
     assert one["GHs"] == 2.0 and one["n"] == 2 and one["others_running"] == [], one
+
+
+def test_bench_main_plain_run_only_times_its_steps(oracle, tmp_path, monkeypatch, capsys):
+    """bench.main() without --full at N = 1, on CPU with a stand-in context:
+    exactly warmup + steps searches, none of what --full adds (no clock
+    measurement, no C4 step, no CPU baseline), ms_per_step and value from the
+    timed steps, and --dump-outputs writes the last step's answer."""
+    import json
+    import types
+    import numpy as np
+    from distributed_bitcoin_minter_amd import _lib
+    LO, HI = 0, 49_999
+    calls = []
+
+    class FakeCtx:
+        def __init__(self, devices=None, **kw):
+            pass
+
+        def set_timing(self, on):
+            pass
+
+        def num_devices(self):
+            return 1
+
+        def close(self):
+            pass
+
+        def search(self, msg, lo, hi):
+            calls.append((lo, hi))
+            return oracle.search(msg, lo, hi)
+
+        def last_stats(self):
+            n = HI - LO + 1
+            L = types.SimpleNamespace(p=18, nbv=1, pad_block=0, digits=5, inner_digits=2, nonces=n, grid=1792,
+                                      tasks_per_thread=1, ms=1.0, clock_ghz=0.0, device=0)
+            return types.SimpleNamespace(
+                nonces=n, span_ms=1.0, combine_used=_lib.BM_COMBINED_LOCAL, rccl_status=0, rccl_nranks=0, rccl_rank=-1,
+                devices=1, dev_nonces=[n], dev_span_ms=[1.0], dev_rccl_rank=[-1], dev_rccl_device=[-1],
+                launches=1, recorded=1, launch=[L])
+
+    def never(*a, **k):
+        raise AssertionError("a plain run does only its timed steps")
+
+    monkeypatch.setattr(bench, "Context", FakeCtx)
+    monkeypatch.setattr(_lib, "load", lambda: None)
+    monkeypatch.setattr(bench, "device_pci_bus_id", lambda d: "0000:10:00.0")
+    monkeypatch.setattr(bench, "workload", lambda cfg, n: (b"bradfitz", LO, HI, "weak", "C2 (shrunk for a CPU test)"))
+    monkeypatch.setattr(bench, "golden", lambda msg, lo, hi: list(oracle.search(msg, lo, hi)))
+    for name in ("measure_clock", "c4_block", "c4_one_process", "cpu_baseline"):
+        monkeypatch.setattr(bench, name, never)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2",
+                                      "--dump-outputs", str(tmp_path / "d")])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls == [(LO, HI)] * 5
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["result_ok"] is True and line["ms_per_step"] > 0
+    assert abs(line["value"] - (HI - LO + 1) / line["ms_per_step"] / 1e6) <= 0.02 * line["value"] + 1e-4
+    assert (line["unit"], line["higher_is_better"], line["dtype"], line["metric"]) == ("GH/s", True, "u32", bench.METRIC)
+    for k in ("c4", "c4_one_process", "cpu_baseline"):
+        assert k not in line, k
+    a = np.load(tmp_path / "d" / "result.npy")
+    assert [(int(a[0]) << 32) | int(a[1]), (int(a[2]) << 32) | int(a[3])] == line["result"]

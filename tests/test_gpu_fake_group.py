@@ -172,7 +172,7 @@ def test_bench_torchrun_joined_group_line():
     env = dict(os.environ, HIP_VISIBLE_DEVICES="0", BTCMINER_LIB=FAKE_LIB)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "2"]
+           "--warmup", "2", "--full"]
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env,
                          start_new_session=True)
     try:

@@ -230,6 +230,27 @@ def _line(r):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """bench.py without --full: the timed steps and the line only (--steps is
+    the number of timed steps, ms_per_step one step's time; no C4 step, no CPU
+    baseline, no clock measurement), and --dump-outputs writes the last
+    step's (hash, nonce) as result.npy, equal to the line's result and C2's
+    golden."""
+    import numpy as np
+    out = _line(_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")]))
+    assert out["result_ok"] is True and out["steps"] == 2 and out["warmup"] == 1
+    assert out["unit"] == "GH/s" and out["higher_is_better"] is True and out["dtype"] == "u32"
+    assert 10 < out["ms_per_step"] < 1000, out["ms_per_step"]  # 2^32 nonces: about 80 ms
+    assert abs(out["value"] - 2 ** 32 / out["ms_per_step"] / 1e6) < 0.01 * out["value"]
+    for k in ("c4", "c4_one_process", "cpu_baseline"):
+        assert k not in out, k
+    assert "clock_ghz_box" not in out["roofline"] and "clock_ghz_box_live" not in out["roofline"]
+    a = np.load(tmp_path / "dump" / "result.npy")
+    assert a.dtype == np.float64 and a.shape == (4,)
+    got = [(int(a[0]) << 32) | int(a[1]), (int(a[2]) << 32) | int(a[3])]
+    assert got == out["result"] == [C2["hash"], C2["nonce"]]
+
+
 def test_bench_one_process_rehearsal():
     """bench.py --gpus 2 without a launcher on a one-GPU box: loud failure,
     unless --rehearse-one-gpu (2-way split on GPU 0); the answer matches the
@@ -238,7 +259,8 @@ def test_bench_one_process_rehearsal():
     if device_count() < 2:
         r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
         assert r.returncode == 2 and "HIP device" in r.stderr
-    out = _line(_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--rehearse-one-gpu"]))
+    out = _line(_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
+                        "--rehearse-one-gpu"]))
     assert out["n_gpus"] == 2 and out["config"]["global_nonces"] == 2 ** 33
     assert out["result_ok"] in (True, None) and "rehearsal" in out
     assert out["scaling_valid"] is False and "rehearsal" in out["scaling_invalid"][0]
@@ -275,7 +297,7 @@ def test_bench_torchrun_rehearsal_c4_one_process():
     design): rank 0 runs it in a child while the ranks idle.  Rehearsed on
     one GPU: 2 slots on GPU 0, host combine, the 2^40 golden, and no scaling
     claim."""
-    out = _line(_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--rehearse-one-gpu"], torchrun=2))
+    out = _line(_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--rehearse-one-gpu"], torchrun=2))
     assert out["result_ok"] is True and out["c4"]["result_ok"] is True, out.get("c4")
     one = out["c4_one_process"]
     assert "skipped" not in one, one
@@ -293,7 +315,7 @@ def test_bench_torchrun_rccl_world1():
     WORLD_SIZE is forced to 1 by the launcher: covered by
     test_rank_context_world1.  Here: the N = 1 line is well formed and maps
     one HIP runtime."""
-    out = _line(_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-c4"]))
+    out = _line(_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-c4"]))
     assert out["result_ok"] is True and out["n_gpus"] == 1 and "c4" not in out
     assert len(out["hip_runtime"]) == 1 and "/opt/rocm" in out["hip_runtime"][0]
     assert out["roofline"]["frac"] > 0.5

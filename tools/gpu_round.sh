@@ -48,40 +48,40 @@ step() {  # name, seconds, command...
   return $rc
 }
 PYTEST="python -u -m pytest -p no:cacheprovider --timeout 300 --timeout-method thread -rs"
-BENCH="python3 bench.py --no-cpu-baseline"
+BENCH="python3 bench.py --full --no-cpu-baseline"
 D=distributed_bitcoin_minter_amd
 for phase in "$@"; do
   case $phase in
     driver)
       step driver_tests 1200 python -m pytest tests/ -x -q -m gpu
       step driver_smoke 240 python -c "import __graft_entry__ as g; g.smoke()"
-      step driver_bench 400 python bench.py ;;
+      step driver_bench 400 python bench.py --full ;;
     smoke) step smoke 240 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step gpu_tests 1200 $PYTEST tests -m gpu -v ;;
     tests_multi) step gpu_tests_multi 600 $PYTEST tests/test_gpu_multi.py -m gpu -v ;;
     tests_k) step gpu_tests_k 600 $PYTEST tests -m gpu -v -k "${TESTS_K}" ;;
-    bench) step bench_C2 300 python -u bench.py --steps 20 --warmup 5 ;;
+    bench) step bench_C2 300 python -u bench.py --full --steps 20 --warmup 5 ;;
     bench_c3) step bench_C3 300 $BENCH --config C3 --steps 20 --warmup 5 ;;
     bench_c4) step bench_C4 300 $BENCH --config C4 --steps 2 --warmup 1 ;;
     rehearse)
       step rehearse2_oneproc 300 $BENCH --gpus 2 --steps 3 --warmup 2 --rehearse-one-gpu
       step rehearse2_mask 400 env HIP_VISIBLE_DEVICES=0 python -u -m torch.distributed.run --nnodes=1 \
-        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 2
+        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 2
       step rehearse8_C4 300 $BENCH --config C4 --gpus 8 --rehearse-one-gpu --steps 1 --warmup 1 ;;
     rehearse8)
       # the driver's N = 8 launch, all 8 ranks masked onto GPU 0 (RCCL refuses: rendezvous gather)
       step rehearse8_torchrun 400 env HIP_VISIBLE_DEVICES=0 python -u -m torch.distributed.run --nnodes=1 \
-        --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --steps 2 --warmup 2 ;;
+        --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 bench.py --full --gpus 8 --steps 2 --warmup 2 ;;
     rehearse_fake)
       # the driver's N = 2 / N = 8 launch shapes with the group JOINED: the
       # library linked against the stand-in RCCL (tests/fake_rccl/), every rank
       # on GPU 0 -- the joined-group path real RCCL refuses on one GPU
       step rehearse2_fakerccl 400 env HIP_VISIBLE_DEVICES=0 BTCMINER_LIB=$PWD/tests/fake_rccl/libbtcminer_fakerccl.so \
         python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 \
-        bench.py --gpus 2 --steps 3 --warmup 2
+        bench.py --full --gpus 2 --steps 3 --warmup 2
       step rehearse8_fakerccl 400 env HIP_VISIBLE_DEVICES=0 BTCMINER_LIB=$PWD/tests/fake_rccl/libbtcminer_fakerccl.so \
         python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29520 \
-        bench.py --gpus 8 --steps 2 --warmup 2 ;;
+        bench.py --full --gpus 8 --steps 2 --warmup 2 ;;
     c5)
       step c5_native 300 python -u tools/bench_c5_native.py
       step c5_python 300 python -u tools/bench_c5.py ;;
@@ -141,11 +141,11 @@ for phase in "$@"; do
       step pmc_summary 60 python3 tools/pmc_summary.py "$OUT" "$OUT" C2 ;;
     rehearse_one)
       step rehearse2_c4_one 400 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29521 bench.py --gpus 2 --steps 2 --warmup 2 --rehearse-one-gpu ;;
+        --master-addr 127.0.0.1 --master-port 29521 bench.py --full --gpus 2 --steps 2 --warmup 2 --rehearse-one-gpu ;;
     rehearse8_one)
       # the driver's N = 8 launch shape, every rank and the one-process child's 8 slots on GPU 0
       step rehearse8_c4_one 500 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-        --master-addr 127.0.0.1 --master-port 29522 bench.py --gpus 8 --steps 2 --warmup 3 --rehearse-one-gpu ;;
+        --master-addr 127.0.0.1 --master-port 29522 bench.py --full --gpus 8 --steps 2 --warmup 3 --rehearse-one-gpu ;;
     pmc_c3)
       C=C3
       step pmc_${C}_fetch 90 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_${C}_fetch" -o f --output-format csv \
