@@ -63,6 +63,15 @@ class Stats(ctypes.Structure):
                 ("launch", LaunchStat * BM_MAX_LAUNCH_STATS)]
 
 
+class TargetResult(ctypes.Structure):
+    _fields_ = [("hash", c_u64), ("nonce", c_u64), ("found", c_i32), ("reserved", c_i32)]
+
+
+class TargetStats(ctypes.Structure):
+    _fields_ = [("nonces_dispatched", c_u64), ("dev_dispatched", c_u64 * BM_MAX_STAT_DEVICES),
+                ("devices", c_u32), ("reserved", c_u32)]
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -132,6 +141,9 @@ def _open(path):
         "bm_reduce_gpu": ([vp, P(Result), ctypes.c_size_t, P(Result)], ctypes.c_int),
         "bm_ctx_set_test_fault": ([vp, ctypes.c_int], ctypes.c_int),
         "bm_search_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, c_u64, c_u64, P(Result)], ctypes.c_int),
+        "bm_search_target_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, c_u64, c_u64, c_u64, P(TargetResult)],
+                                 ctypes.c_int),
+        "bm_ctx_last_target_stats": ([vp, P(TargetStats)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -150,7 +162,10 @@ def _open(path):
                                  ctypes.c_int, P(ctypes.c_int)], ctypes.c_int),
     }
     for name, (args, res) in sigs.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # a build from before the call was added (the ABI version did not change)
+            raise OSError(f"{path}: no {name}; rebuild it") from None
         fn.argtypes = args
         fn.restype = res
     # the stats structs above are this ABI's layout: any other build (an
@@ -324,6 +339,21 @@ class Context:
         r = Result()
         check(self._lib.bm_search_gpu(self.handle, msg, len(msg), lower, upper, ctypes.byref(r)), "bm_search_gpu")
         return r.hash, r.nonce
+
+    def search_target(self, msg: bytes, lower: int, upper: int, target: int):
+        """The first nonce of [lower, upper] whose hash is <= target ->
+        (True, hash, nonce); none -> (False, min hash, its nonce), the answer
+        of search()."""
+        r = TargetResult()
+        check(self._lib.bm_search_target_gpu(self.handle, msg, len(msg), lower, upper, target, ctypes.byref(r)),
+              "bm_search_target_gpu")
+        return bool(r.found), r.hash, r.nonce
+
+    def last_target_stats(self):
+        """How much of the range the last search_target() handed out."""
+        s = TargetStats()
+        check(self._lib.bm_ctx_last_target_stats(self.handle, ctypes.byref(s)), "bm_ctx_last_target_stats")
+        return s
 
     def hash_many(self, msg: bytes, nonces):
         n = len(nonces)

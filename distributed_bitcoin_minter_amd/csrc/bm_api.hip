@@ -38,6 +38,9 @@ namespace bm {
 // message) and search_kernel_padk<P, K> (K = 1..kMaxPadPrefixBlocks = 15)
 constexpr int kSearchRows = 3 + kMaxPadPrefixBlocks;
 static const void* g_search[kSearchRows][64];
+// target_kernel<P, NBV> table [nbv-1][P] (bm_search_target_gpu): the generic
+// kernel in target mode, every layout
+static const void* g_target[2][64];
 
 constexpr int kMaxInnerDigits = 2;  // S <= 100 nonces per task: small dequeue chunks, short tail
 constexpr uint32_t kNoncesPerLaneChunk = 100;  // default nonces per lane per dequeue (BTCMINER_CHUNK)
@@ -81,6 +84,9 @@ struct DeviceCtx {
                                           // counter, [16..19] clock stamps (bm_kernels.hpp)
     unsigned long long* h_ctr = nullptr;  // pinned copy of the strips (timing on)
     size_t ctr_cap = 0;
+    unsigned long long* d_hit = nullptr;  // target search: the lowest nonce at or below the target seen so
+                                          // far (all-ones: none); an allocation, hence a line, of its own
+    unsigned long long* h_hit = nullptr;  // pinned copy
     Slot* d_slot = nullptr;    // this device's slot (reduce_partials writes its partial)
     Slot* d_gather = nullptr;  // nslots slots (allgather target)
     Slot* h_slots = nullptr;   // pinned: nslots slots, + 1 staging slot (a failed rank's status)
@@ -268,12 +274,17 @@ struct bm_ctx {
     std::shared_ptr<bm::JoinJob> pending_join;
     std::thread pending_worker;
     bm_stats_t stats;
+    bm_target_stats_t tstats;  // the last bm_search_target_gpu (zero after a failed one)
     bm::SubmitPool submit;  // multi-device: one submission thread per device but the first (last member:
                             // stopped first, when every device is idle)
 };
 
 extern "C" void bm_register_search_kernel(int p, int nbv, const void* fn) {
     if (p >= 0 && p < 64 && nbv >= 1 && nbv <= bm::kSearchRows) bm::g_search[nbv - 1][p] = fn;
+}
+
+extern "C" void bm_register_target_kernel(int p, int nbv, const void* fn) {
+    if (p >= 0 && p < 64 && nbv >= 1 && nbv <= 2) bm::g_target[nbv - 1][p] = fn;
 }
 
 namespace bm {
@@ -316,14 +327,15 @@ int pad_fold_k(const bm_segment_t& s) {
     return (int)k;
 }
 
-int size_launch(bm_ctx* ctx, DeviceCtx& d, const bm_segment_t& s, uint32_t part_off, Launch& L) {
+int size_launch(bm_ctx* ctx, DeviceCtx& d, const bm_segment_t& s, uint32_t part_off, Launch& L,
+                bool target = false) {
     // the folded kernel where it applies and this build registered it (an
     // A/B build may instantiate only some layouts): else the generic one,
-    // which gives the same answer
-    const int fk = ctx->padc ? pad_fold_k(s) : -1;
+    // which gives the same answer.  A target search has generic kernels only.
+    const int fk = (ctx->padc && !target) ? pad_fold_k(s) : -1;
     const void* fn = fk >= 0 ? g_search[2 + fk][s.p] : nullptr;
     const bool padc = fn != nullptr;
-    if (!fn) fn = g_search[s.nbv - 1][s.p];
+    if (!fn) fn = target ? g_target[s.nbv - 1][s.p] : g_search[s.nbv - 1][s.p];
     if (!fn) return BM_EINTERNAL;
     int ms = std::max(1, std::min(s.max_inner, kMaxInnerDigits));
     // word LW holds one digit: the kernel steps the next one in word LW-1
@@ -427,6 +439,8 @@ int init_device(DeviceCtx& d, int id, int nslots) {
     BM_HIP(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
     d.nslots = nslots;
     BM_HIP(hipMalloc(&d.d_slot, sizeof(Slot)));
+    BM_HIP(hipMalloc(&d.d_hit, 128));
+    BM_HIP(hipHostMalloc(&d.h_hit, sizeof(unsigned long long), hipHostMallocDefault));
     BM_HIP(hipMalloc(&d.d_gather, sizeof(Slot) * (size_t)nslots));
     BM_HIP(hipHostMalloc(&d.h_slots, sizeof(Slot) * (size_t)(nslots + 1), hipHostMallocDefault));
     for (auto& e : d.ev) BM_HIP(hipEventCreate(&e));
@@ -458,6 +472,8 @@ void destroy_device(DeviceCtx& d) {
     if (d.d_ctr) (void)hipFree(d.d_ctr);
     if (d.h_ctr) (void)hipHostFree(d.h_ctr);
     if (d.d_slot) (void)hipFree(d.d_slot);
+    if (d.d_hit) (void)hipFree(d.d_hit);
+    if (d.h_hit) (void)hipHostFree(d.h_hit);
     if (d.d_gather) (void)hipFree(d.d_gather);
     if (d.d_hash_io) (void)hipFree(d.d_hash_io);
     if (d.d_test) (void)hipFree(d.d_test);
@@ -582,8 +598,11 @@ void drain(bm_ctx* ctx) {
 // Stage 2 of a search, one device: enqueue its launches and its second-pass
 // reduction (its partial lands in d_slot).  `enqueued` counts launches over
 // every device (the test fault).  On failure the caller drains.
+// target != nullptr (bm_search_target_gpu): the target kernels, enqueued in
+// ascending nonce order so that a hit cancels what lies above it; the hit
+// word and the dequeue counters come back with the partial.
 int enqueue_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, uint32_t& first,
-                   std::atomic<int>& enqueued) {
+                   std::atomic<int>& enqueued, const uint64_t* target) {
     DeviceCtx& d = ctx->devs[di];
     const bool mark = ctx->balance || ctx->timing;  // per-device span events
     BM_HIP(hipSetDevice(d.id));
@@ -595,13 +614,25 @@ int enqueue_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, uint32_t&
     uint32_t nparts = 0, li = 0;
     if (!launches.empty())
         BM_HIP(hipMemsetAsync(d.d_ctr, 0, launches.size() * kCtrStride * sizeof(unsigned long long), d.stream));
-    // stream of each launch: biggest first, round-robin over the streams
+    if (target) {
+        *d.h_hit = ~0ull;
+        BM_HIP(hipMemsetAsync(d.d_hit, 0xFF, sizeof(unsigned long long), d.stream));
+    }
+    // stream of each launch: biggest first (a target search: lowest nonces
+    // first), round-robin over the streams
     const int ns = std::max(1, std::min<int>(ctx->streams, (int)launches.size()));
     std::vector<uint32_t> order(launches.size());
     for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
+    if (target)
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+            const SearchArgs &a = launches[x].args, &b = launches[y].args;
+            return a.nonce_base + a.vlo < b.nonce_base + b.vlo;
+        });
     if (ns > 1) {
-        std::stable_sort(order.begin(), order.end(),
-                         [&](uint32_t x, uint32_t y) { return launches[x].stat.nonces > launches[y].stat.nonces; });
+        if (!target)
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+                return launches[x].stat.nonces > launches[y].stat.nonces;
+            });
         BM_HIP(hipEventRecord(d.fork, d.stream));
         for (int k = 0; k + 1 < ns; ++k) BM_HIP(hipStreamWaitEvent(d.aux[k], d.fork, 0));
     }
@@ -614,8 +645,10 @@ int enqueue_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, uint32_t&
         const bool timed = ctx->timing && li < (uint32_t)kEventPairs;
         if (timed) BM_HIP(hipEventRecord(d.ev[2 * li], s));
         unsigned long long* ctr = d.d_ctr + kCtrStride * li;
+        uint64_t tgt = target ? *target : 0;
         void* kargs[] = {&L.args, &d.d_part, &ctr};
-        BM_HIP(hipLaunchKernel(L.fn, dim3(L.grid), dim3(kBlock), kargs, 0, s));
+        void* targs[] = {&L.args, &d.d_part, &ctr, &tgt, &d.d_hit};  // target_kernel's
+        BM_HIP(hipLaunchKernel(L.fn, dim3(L.grid), dim3(kBlock), target ? targs : kargs, 0, s));
         if (timed) BM_HIP(hipEventRecord(d.ev[2 * li + 1], s));
         nparts += L.grid;
     }
@@ -627,7 +660,9 @@ int enqueue_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, uint32_t&
     reduce_partials<<<1, kReduceThreads, 0, d.stream>>>(d.d_part, nparts, &d.d_slot->p);
     BM_HIP(hipGetLastError());
     if (mark) BM_HIP(hipEventRecord(d.bal[1], d.stream));
-    if (BM_CLOCK_PROBE && ctx->timing && !launches.empty())  // clock stamps, for the launch stats
+    if (target) BM_HIP(hipMemcpyAsync(d.h_hit, d.d_hit, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+    // clock stamps, for the launch stats; a target search: the dequeue counters
+    if (((BM_CLOCK_PROBE && ctx->timing) || target) && !launches.empty())
         BM_HIP(hipMemcpyAsync(d.h_ctr, d.d_ctr, launches.size() * kCtrStride * sizeof(unsigned long long),
                               hipMemcpyDeviceToHost, d.stream));
     return BM_OK;
@@ -654,12 +689,15 @@ int guarded(F&& f) noexcept {
 // wait for the other devices' ~15 API calls each before it starts (the start
 // skew of a serial submission; bm_stats_t.dev_start_ms reports what is left
 // of it).
-int enqueue(bm_ctx* ctx, std::vector<std::vector<Launch>>& launches, std::vector<uint32_t>& first) {
+int enqueue(bm_ctx* ctx, std::vector<std::vector<Launch>>& launches, std::vector<uint32_t>& first,
+            const uint64_t* target = nullptr) {
     const int ndev = (int)ctx->devs.size();
     if (ctx->fault_after == 0) return BM_EINTERNAL;  // test hook (also for a rank with nothing to scan)
     std::atomic<int> enqueued{0};
     ctx->stats.start_threads = 1;
-    auto one = [&](int di) { return guarded([&] { return enqueue_device(ctx, di, launches[di], first[di], enqueued); }); };
+    auto one = [&](int di) {
+        return guarded([&] { return enqueue_device(ctx, di, launches[di], first[di], enqueued, target); });
+    };
     if (ndev == 1) return one(0);
     std::vector<int> rc(ndev, BM_OK);
     const std::function<void(int)> job = [&](int di) { rc[di] = one(di); };
@@ -729,13 +767,14 @@ Partial lex_min_slots(const Slot* s, int n) {
 // RCCL allgather, or by host copies (BM_COMBINE_HOST, a device listed twice,
 // or RCCL failing at run time: the context then aborts its communicators and
 // stays on host copies, reported in the stats).  A rank context outside a
-// group copies its own partial.
-int combine_local(bm_ctx* ctx, Partial* best_out) {
+// group copies its own partial.  host_only (a target search): host copies,
+// whatever the context's combine mode.
+int combine_local(bm_ctx* ctx, Partial* best_out, bool host_only = false) {
     bm_stats_t& st = ctx->stats;
     const int ndev = (int)ctx->devs.size();
     int nslots = ndev;
     bool via_rccl = false;
-    if (!ctx->rank_ctx) {
+    if (!ctx->rank_ctx && !host_only) {
         const bool distinct = distinct_devices(ctx);
         if (ctx->combine == BM_COMBINE_RCCL && !distinct) return BM_EINVAL;
         const bool want = ctx->combine == BM_COMBINE_RCCL || (ctx->combine == BM_COMBINE_AUTO && ndev > 1 && distinct);
@@ -784,7 +823,7 @@ int combine_local(bm_ctx* ctx, Partial* best_out) {
                 return rc;
             }
         }
-    } else {
+    } else if (ctx->rank_ctx) {
         nslots = 1;  // a rank outside a group: its own partial
     }
     if (!via_rccl) {
@@ -916,7 +955,7 @@ int combine_group(bm_ctx* ctx, int own_rc, Partial* best_out) {
 // the devices (the partitioner: slot_pieces over ctx->shares; an empty piece
 // has lo > hi); plan and size every launch.
 int plan_launches(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
-                  std::vector<std::vector<Launch>>& launches) {
+                  std::vector<std::vector<Launch>>& launches, bool target = false) {
     bm_stats_t& st = ctx->stats;
     const int ndev = (int)ctx->devs.size();
     uint64_t lo = lower, hi = upper;
@@ -955,7 +994,7 @@ int plan_launches(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, u
         uint32_t off = 0;
         for (const auto& s : segs) {
             Launch L;
-            rc = size_launch(ctx, ctx->devs[di], s, off, L);
+            rc = size_launch(ctx, ctx->devs[di], s, off, L, target);
             if (rc != BM_OK) return rc;
             L.stat.device = di;
             off += L.grid;
@@ -987,6 +1026,61 @@ void stamp_common(bm_ctx* ctx) {
     const bool have = ctx->rank_ctx ? ctx->joined && ctx->devs[0].comm != nullptr : ctx->nccl_ready;
     st.rccl_init_ms = have ? ctx->rccl_init_ms : 0.0;
     if (st.start_threads == 0) st.start_threads = 1;
+}
+
+// Each device's start against the earliest device's (host submission times).
+std::vector<double> start_offsets(bm_ctx* ctx) {
+    const int ndev = (int)ctx->devs.size();
+    std::vector<double> start_ms(ndev, 0.0);
+    auto t0 = ctx->devs[0].submitted;
+    for (const auto& d : ctx->devs) t0 = std::min(t0, d.submitted);
+    for (int di = 0; di < ndev; ++di)
+        start_ms[di] = std::chrono::duration<double, std::milli>(ctx->devs[di].submitted - t0).count();
+    return start_ms;
+}
+
+// The statistics of a finished call (a search or a target search): devices,
+// launch list, event timings, wall time.
+int record_stats(bm_ctx* ctx, std::vector<std::vector<Launch>>& launches, const std::vector<uint32_t>& first,
+                 const std::vector<double>& start_ms, std::chrono::steady_clock::time_point t_start) {
+    bm_stats_t& st = ctx->stats;
+    const int ndev = (int)ctx->devs.size();
+    st.devices = (uint32_t)std::min(ndev, BM_MAX_STAT_DEVICES);
+    for (int di = 0; di < ndev; ++di) {
+        DeviceCtx& d = ctx->devs[di];
+        if (di < BM_MAX_STAT_DEVICES) {
+            st.dev_nonces[di] = d.piece_nonces;
+            if (ctx->timing || ctx->balance) st.dev_start_ms[di] = start_ms[di];
+            float ms = 0.f;
+            if ((ctx->timing || ctx->balance) && hipSetDevice(d.id) == hipSuccess &&
+                hipEventElapsedTime(&ms, d.bal[0], d.bal[1]) == hipSuccess)
+                st.dev_span_ms[di] = ms;
+        }
+        uint32_t li = 0;
+        const bool span_ok = ctx->timing && !launches[di].empty() && first[di] < (uint32_t)kEventPairs;
+        for (Launch& L : launches[di]) {
+            ++st.launches;
+            if (ctx->timing && li < (uint32_t)kEventPairs) {
+                float ms = 0.f;
+                BM_HIP(hipEventElapsedTime(&ms, d.ev[2 * li], d.ev[2 * li + 1]));
+                L.stat.ms = ms;
+                st.kernel_ms += ms;
+                const unsigned long long* c = d.h_ctr + kCtrStride * li + kClockSlot - 1;
+                if (BM_CLOCK_PROBE && c[4] > c[2] && c[3] > c[1])  // shader cycles over constant-rate ticks
+                    L.stat.clock_ghz = (double)(c[3] - c[1]) / ((double)(c[4] - c[2]) / d.wall_clock_hz) / 1e9;
+                if (span_ok) {  // the first launch's start to this launch's end
+                    float sp = 0.f;
+                    BM_HIP(hipEventElapsedTime(&sp, d.ev[2 * first[di]], d.ev[2 * li + 1]));
+                    st.span_ms = std::max(st.span_ms, (double)sp);
+                }
+            }
+            if (st.recorded < BM_MAX_LAUNCH_STATS) st.launch[st.recorded++] = L.stat;
+            ++li;
+        }
+    }
+    stamp_common(ctx);
+    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return BM_OK;
 }
 
 int search_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, bm_result_t* out) {
@@ -1041,14 +1135,7 @@ int search_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uin
         }
     }
 
-    // each device's start against the earliest device's (host submission times)
-    std::vector<double> start_ms(ndev, 0.0);
-    {
-        auto t0 = ctx->devs[0].submitted;
-        for (const auto& d : ctx->devs) t0 = std::min(t0, d.submitted);
-        for (int di = 0; di < ndev; ++di)
-            start_ms[di] = std::chrono::duration<double, std::milli>(ctx->devs[di].submitted - t0).count();
-    }
+    const std::vector<double> start_ms = start_offsets(ctx);
 
     // 4. balance: the next call's shares follow each device's measured rate,
     // its nonces over the time from the call's common start to its reduction,
@@ -1077,43 +1164,102 @@ int search_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uin
     }
 
     // 5. statistics
-    st.devices = (uint32_t)std::min(ndev, BM_MAX_STAT_DEVICES);
-    for (int di = 0; di < ndev; ++di) {
-        DeviceCtx& d = ctx->devs[di];
-        if (di < BM_MAX_STAT_DEVICES) {
-            st.dev_nonces[di] = d.piece_nonces;
-            if (ctx->timing || ctx->balance) st.dev_start_ms[di] = start_ms[di];
-            float ms = 0.f;
-            if ((ctx->timing || ctx->balance) && hipSetDevice(d.id) == hipSuccess &&
-                hipEventElapsedTime(&ms, d.bal[0], d.bal[1]) == hipSuccess)
-                st.dev_span_ms[di] = ms;
-        }
-        uint32_t li = 0;
-        const bool span_ok = ctx->timing && !launches[di].empty() && first[di] < (uint32_t)kEventPairs;
-        for (Launch& L : launches[di]) {
-            ++st.launches;
-            if (ctx->timing && li < (uint32_t)kEventPairs) {
-                float ms = 0.f;
-                BM_HIP(hipEventElapsedTime(&ms, d.ev[2 * li], d.ev[2 * li + 1]));
-                L.stat.ms = ms;
-                st.kernel_ms += ms;
-                const unsigned long long* c = d.h_ctr + kCtrStride * li + kClockSlot - 1;
-                if (BM_CLOCK_PROBE && c[4] > c[2] && c[3] > c[1])  // shader cycles over constant-rate ticks
-                    L.stat.clock_ghz = (double)(c[3] - c[1]) / ((double)(c[4] - c[2]) / d.wall_clock_hz) / 1e9;
-                if (span_ok) {  // the first launch's start to this launch's end
-                    float sp = 0.f;
-                    BM_HIP(hipEventElapsedTime(&sp, d.ev[2 * first[di]], d.ev[2 * li + 1]));
-                    st.span_ms = std::max(st.span_ms, (double)sp);
-                }
-            }
-            if (st.recorded < BM_MAX_LAUNCH_STATS) st.launch[st.recorded++] = L.stat;
-            ++li;
-        }
-    }
-    stamp_common(ctx);
-    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    rc = record_stats(ctx, launches, first, start_ms, t_start);
+    if (rc != BM_OK) return rc;
     out->hash = best.hash;
     out->nonce = best.nonce;
+    return BM_OK;
+}
+
+// bitcoin.Hash(msg, nonce) on the host (hash.go:11-15: the first 8 bytes,
+// big-endian, of SHA-256("msg nonce")), with the compression the planner
+// uses for midstates: once per found target, never per nonce.
+uint64_t host_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
+    char dec[24];
+    const int nd = std::snprintf(dec, sizeof dec, "%llu", (unsigned long long)nonce);
+    const uint64_t total = (uint64_t)len + 1 + (uint64_t)nd;
+    auto byte_at = [&](uint64_t pos) -> uint8_t {
+        if (pos < len) return msg[pos];
+        if (pos == len) return (uint8_t)' ';
+        if (pos < total) return (uint8_t)dec[pos - len - 1];
+        return pos == total ? 0x80 : 0;
+    };
+    const uint64_t blocks = (total + 1 + 8 + 63) / 64;  // data, the 0x80 byte, the 64-bit length
+    uint32_t st[8];
+    for (int i = 0; i < 8; ++i) st[i] = kIV256[i];
+    uint8_t blk[64];
+    for (uint64_t b = 0; b < blocks; ++b) {
+        for (int i = 0; i < 64; ++i) blk[i] = byte_at(b * 64 + (uint64_t)i);
+        if (b + 1 == blocks)
+            for (int i = 0; i < 8; ++i) blk[56 + i] = (uint8_t)((total * 8) >> (8 * (7 - i)));
+        host::compress_bytes(st, blk);
+    }
+    return ((uint64_t)st[0] << 32) | st[1];
+}
+
+// bm_search_target_gpu: search_impl's stages with the target kernels.  Each
+// device scans its piece in ascending launch order with a hit word of its
+// own; the host takes the lowest-nonce hit (pieces ascend with the device
+// index), or the lexicographic min of the partials when there is none.
+int target_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
+                bm_target_result_t* out) {
+    const auto t_start = std::chrono::steady_clock::now();
+    bm_stats_t& st = ctx->stats;
+    bm_target_stats_t& ts = ctx->tstats;
+    std::memset(&st, 0, sizeof st);
+    std::memset(&ts, 0, sizeof ts);
+    record_rccl(ctx, false);
+    const int ndev = (int)ctx->devs.size();
+    if (lower > upper) {
+        stamp_common(ctx);
+        *out = bm_target_result_t{UINT64_MAX, UINT64_MAX, 0, 0};
+        return BM_OK;
+    }
+
+    std::vector<std::vector<Launch>> launches(ndev);
+    std::vector<uint32_t> first(ndev, 0);
+    Partial best{UINT64_MAX, UINT64_MAX};
+    int rc = guarded([&] { return plan_launches(ctx, msg, len, lower, upper, launches, true); });
+    if (rc == BM_OK) rc = enqueue(ctx, launches, first, &target);
+    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
+    if (rc == BM_OK) rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
+    if (rc != BM_OK) {
+        drain(ctx);
+        std::memset(&st, 0, sizeof st);
+        record_rccl(ctx, false);
+        stamp_common(ctx);
+        return rc;
+    }
+
+    uint64_t hit = UINT64_MAX;
+    bool found = false;
+    ts.devices = (uint32_t)std::min(ndev, BM_MAX_STAT_DEVICES);
+    for (int di = 0; di < ndev; ++di) {
+        DeviceCtx& d = ctx->devs[di];
+        if (launches[di].empty()) continue;
+        if (*d.h_hit != UINT64_MAX && !found) {
+            hit = *d.h_hit;
+            found = true;
+        }
+        uint64_t disp = 0;
+        for (size_t li = 0; li < launches[di].size(); ++li) {
+            const Launch& L = launches[di][li];
+            const uint64_t tasks = std::min<uint64_t>(d.h_ctr[kCtrStride * li], L.args.t_end - L.args.t0);
+            disp += std::min<uint64_t>(tasks * (uint64_t)L.args.S, L.stat.nonces);
+        }
+        if (di < BM_MAX_STAT_DEVICES) ts.dev_dispatched[di] = disp;
+        ts.nonces_dispatched += disp;
+    }
+    // the nonce 2^64-1 cannot be told from "none" in the hit word: it is the
+    // answer exactly when nothing below it hit and its own hash meets the target
+    if (!found && upper == UINT64_MAX && host_hash(msg, len, UINT64_MAX) <= target) {
+        hit = UINT64_MAX;
+        found = true;
+    }
+    if (found)
+        *out = bm_target_result_t{host_hash(msg, len, hit), hit, 1, 0};
+    else
+        *out = bm_target_result_t{best.hash, best.nonce, 0, 0};
     return BM_OK;
 }
 
@@ -1267,6 +1413,7 @@ int create_ctx(const int* devices, int n, int nslots, bm_ctx** out) {
     bm_ctx* ctx = new (std::nothrow) bm_ctx();
     if (!ctx) return BM_ENOMEM;
     std::memset(&ctx->stats, 0, sizeof ctx->stats);
+    std::memset(&ctx->tstats, 0, sizeof ctx->tstats);
     record_rccl(ctx, false);
     read_env(ctx);
     DeviceGuard guard;
@@ -1471,6 +1618,23 @@ int bm_search_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower,
     int rc = bm::guarded([&] { return bm::search_impl(ctx, msg, len, lower, upper, &r); });
     if (rc == BM_OK) *out = r;
     return rc;
+}
+
+int bm_search_target_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                         uint64_t target, bm_target_result_t* out) {
+    if (!ctx || !out || (len && !msg) || len > BM_MAX_MSG_LEN) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // the group's allgather slot carries no hit
+    bm::DeviceGuard guard;
+    bm_target_result_t r;
+    int rc = bm::guarded([&] { return bm::target_impl(ctx, msg, len, lower, upper, target, &r); });
+    if (rc == BM_OK) *out = r;
+    return rc;
+}
+
+int bm_ctx_last_target_stats(const bm_ctx_t* ctx, bm_target_stats_t* out) {
+    if (!ctx || !out) return BM_EINVAL;
+    *out = ctx->tstats;
+    return BM_OK;
 }
 
 int bm_reduce_gpu(bm_ctx_t* ctx, const bm_result_t* parts, size_t n, bm_result_t* out) {

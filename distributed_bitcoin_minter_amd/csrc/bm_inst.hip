@@ -15,7 +15,11 @@
 // instk_* units), so each of the many such kernels builds in parallel with
 // the others.
 
+// BM_INST_TARGET: this unit instantiates ONLY target_kernel<P, NBV> (the
+// Makefile's instt1_* / instt2_* units), registered into a table of its own.
+
 extern "C" void bm_register_search_kernel(int p, int nbv, const void* fn);
+extern "C" void bm_register_target_kernel(int p, int nbv, const void* fn);
 
 #include <utility>
 
@@ -24,7 +28,12 @@ namespace {
 // folded, after K whole prefix blocks (K = 0: search_kernel_padc<P>, a
 // one-block message; K = 1, 2: search_kernel_padk<P, K> in the NBV = 1 units,
 // K = 3..15 in the instk_* units); NBV = 1 ranges only
-#ifdef BM_INST_PADK_LO
+#if defined(BM_INST_TARGET)
+template <int P>
+void register_one() {
+    bm_register_target_kernel(P, BM_INST_NBV, reinterpret_cast<const void*>(&bm::target_kernel<P, BM_INST_NBV>));
+}
+#elif defined(BM_INST_PADK_LO)
 template <int P, int K>
 void register_padk() {
     static_assert(P >= 55 && K >= BM_INST_PADK_LO && K <= BM_INST_PADK_HI, "padk unit");

@@ -375,8 +375,23 @@ constexpr int kClockSlot = 16;
 // constants instead of 64 kernargs (kPadKW<P, PADK>; the launcher checks the
 // segment's pad_w against them), and for PADK = 0 the entering state is the
 // IV, also folded.  PADK = -1: the generic kernel, everything from kernargs.
-template <int P, int NBV, int PADK>
-BM_DEV void search_body(const SearchArgs& A, Partial* __restrict__ part, unsigned long long* __restrict__ counter) {
+//
+// TGT (target_kernel): besides the running minimum, the first nonce whose
+// hash is <= target.  `hit` is one word per device and call, all-ones until
+// a lane records a nonce there with atomicMin:
+//  * on the rare path only.  A lane visits its nonces in ascending order, and
+//    every in-range hash before its first hit is above target, so its best is
+//    still at or above the hit's high word and the hit takes the rare branch.
+//    (Later hits of the lane may not; they lie at higher nonces.)
+//  * at each dequeue lane 0 also reads the word (relaxed); a wave whose chunk
+//    starts above the recorded nonce leaves, because chunks only ascend.  Only
+//    nonces strictly above a recorded hit are ever skipped and the word only
+//    decreases, so the smallest hit is always hashed and recorded, whenever
+//    each wave happens to see the word.  Nothing waits on another wave.
+template <int P, int NBV, int PADK, bool TGT = false>
+BM_DEV void search_body(const SearchArgs& A, Partial* __restrict__ part, unsigned long long* __restrict__ counter,
+                        uint64_t target = 0, unsigned long long* hit = nullptr) {
+    static_assert(!TGT || PADK == -1, "target mode runs the generic kernels");
     static_assert(P >= 0 && P < 64 && (NBV == 1 || (NBV == 2 && P <= 18)), "layout");
     constexpr int LW = P / 4;                      // last-block word holding the last digit
     constexpr int BOFF = 16 * (NBV - 1);           // word offset of the last block
@@ -433,9 +448,23 @@ BM_DEV void search_body(const SearchArgs& A, Partial* __restrict__ part, unsigne
     }
     for (;;) {
         uint64_t base = 0;
-        if (lane == 0) base = atomicAdd(counter, (unsigned long long)chunk);
-        base = readfirstlane_u64(base);
-        if (base >= ntask) break;
+        if constexpr (TGT) {
+            uint64_t seen = 0;
+            if (lane == 0) {
+                base = atomicAdd(counter, (unsigned long long)chunk);
+                seen = __hip_atomic_load(hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            base = readfirstlane_u64(base);
+            if (base >= ntask) break;
+            seen = readfirstlane_u64(seen);
+            // in v space, so a range ending at 2^64-1 cannot wrap: the chunk's
+            // lowest v is (t0 + base) * S <= vhi
+            if (seen < A.nonce_base || seen - A.nonce_base < (A.t0 + base) * (uint64_t)S) break;
+        } else {
+            if (lane == 0) base = atomicAdd(counter, (unsigned long long)chunk);
+            base = readfirstlane_u64(base);
+            if (base >= ntask) break;
+        }
         for (uint32_t i = 0; i < A.chunk_m; ++i) {
             const uint64_t tt = base + 64ull * i + lane;
             if (tt >= ntask) break;
@@ -539,6 +568,10 @@ BM_DEV void search_body(const SearchArgs& A, Partial* __restrict__ part, unsigne
                     if (__builtin_expect(h0 <= bh, 0)) {
                         const uint64_t h = ((uint64_t)h0 << 32) | h1;
                         const uint64_t v = vbase + (uint64_t)jo * n_in + j;
+                        if constexpr (TGT) {
+                            if (h <= target && v >= A.vlo && v <= A.vhi)
+                                atomicMin(hit, (unsigned long long)(A.nonce_base + v));
+                        }
 #if BM_LDS_BEST
                         if (h < lbest_h[threadIdx.x] && v >= A.vlo && v <= A.vhi) {
                             lbest_h[threadIdx.x] = h;
@@ -611,6 +644,16 @@ __global__ __launch_bounds__(kBlock) BM_KATTR void search_kernel_padk(
     const SearchArgs A, Partial* __restrict__ part, unsigned long long* __restrict__ counter) {
     static_assert(NBV == 1 && P >= 55 && K >= 1 && K <= kMaxPadPrefixBlocks, "padding-block layouts only");
     search_body<P, 1, K>(A, part, counter);
+}
+
+// The generic kernel in target mode (search_body's TGT), for every layout:
+// the padding-block ones (P >= 55) run here whatever their prefix blocks.
+// Occupancy request as for search_kernel.
+template <int P, int NBV>
+__global__ __launch_bounds__(kBlock) BM_KATTR void target_kernel(
+    const SearchArgs A, Partial* __restrict__ part, unsigned long long* __restrict__ counter, const uint64_t target,
+    unsigned long long* __restrict__ hit) {
+    search_body<P, NBV, -1, true>(A, part, counter, target, hit);
 }
 
 }  // namespace bm

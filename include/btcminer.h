@@ -156,6 +156,40 @@ int bm_ctx_num_devices(const bm_ctx_t* ctx, int* out);
 int bm_search_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
                   bm_result_t* out);
 
+/* ---- target search: the first nonce whose hash meets a target ------------
+ * bm_search_target_gpu scans [lower, upper] for Hash(msg, n) <= target (full
+ * 64-bit unsigned compare) and stops scanning above a hit once one is known.
+ *   found = 1: nonce is the SMALLEST n in [lower, upper] with Hash(msg, n) <=
+ *     target and hash = Hash(msg, nonce): what a sequential ascending scan
+ *     that stops at its first hit returns.
+ *   found = 0: no nonce meets the target; (hash, nonce) is exactly
+ *     bm_search_gpu's answer for the range (all of it was scanned).
+ *   lower > upper: found = 0, {2^64-1, 2^64-1}.  target = 2^64-1 always finds
+ *     lower.  upper = 2^64-1 is legal.
+ * The result never depends on timing, residency, streams, task digits,
+ * max_windows or the split.  On failure `out` is untouched and the context
+ * stays usable; the next bm_search_gpu on the context is unaffected.
+ * Contexts: one device, or one process over several devices (a device listed
+ * N times included): each device scans its piece with a hit word of its own
+ * and the host takes the lowest-nonce hit, or the lexicographic min of the
+ * partials when no device found one -- always by host copies, whatever
+ * bm_ctx_set_combine says.  A hit on one device does NOT cancel another
+ * device's work in flight (out of scope: every device still ends within its
+ * own piece).  A rank context with world > 1 returns BM_EINVAL, joined or
+ * not: the group's 32-byte allgather slot carries no hit.
+ * bm_ctx_set_balance does not learn from target calls (their spans say
+ * nothing about a device's rate); bm_ctx_set_test_fault applies as for a
+ * search.  bm_ctx_last_stats is filled as for a search (the launch list). */
+typedef struct bm_target_result {
+    uint64_t hash;     /* found: Hash(msg, nonce); else the range's minimum hash */
+    uint64_t nonce;    /* found: the first nonce at or below target; else the minimum's nonce */
+    int32_t found;     /* 1: some nonce of the range has Hash <= target */
+    int32_t reserved;  /* 0 */
+} bm_target_result_t;
+
+int bm_search_target_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                         uint64_t target, bm_target_result_t* out);
+
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */
 int bm_hash_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,
@@ -248,6 +282,21 @@ typedef struct bm_stats {
 /* Enable per-launch HIP event timing (default off). */
 int bm_ctx_set_timing(bm_ctx_t* ctx, int enable);
 int bm_ctx_last_stats(const bm_ctx_t* ctx, bm_stats_t* out);
+
+/* How much of the range the last bm_search_target_gpu handed out to waves.
+ * Summed over a device's launches; each launch contributes min(its final
+ * dequeue counter, its task count) x nonces per task, capped at the launch's
+ * own nonce count (read back from the counters the kernels use anyway).  An
+ * upper bound on the nonces hashed: equal to the range size when nothing was
+ * found, and at least nonce - lower + 1 on the device that holds the hit.
+ * Zero after a failed call or an empty range. */
+typedef struct bm_target_stats {
+    uint64_t nonces_dispatched;                    /* all devices */
+    uint64_t dev_dispatched[BM_MAX_STAT_DEVICES];  /* each device of the context */
+    uint32_t devices;                              /* entries of dev_dispatched */
+    uint32_t reserved;
+} bm_target_stats_t;
+int bm_ctx_last_target_stats(const bm_ctx_t* ctx, bm_target_stats_t* out);
 
 /* Occupancy override for the search kernels: workgroups of 256 threads kept
  * resident per CU (0 = ask the runtime).  Exposed for tuning. */

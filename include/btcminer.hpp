@@ -105,6 +105,20 @@ class Context {
               "bm_search_gpu");
         return Result{r.hash, r.nonce};
     }
+    // the first n in [lower, upper] with Hash(msg, n) <= target (found = 1), or
+    // the range's minimum when there is none (found = 0): bm_search_target_gpu
+    bm_target_result_t search_target(std::string_view msg, uint64_t lower, uint64_t upper, uint64_t target) {
+        bm_target_result_t r;
+        check(bm_search_target_gpu(ctx_, reinterpret_cast<const uint8_t*>(msg.data()), msg.size(), lower, upper,
+                                   target, &r),
+              "bm_search_target_gpu");
+        return r;
+    }
+    bm_target_stats_t last_target_stats() const {
+        bm_target_stats_t s;
+        check(bm_ctx_last_target_stats(ctx_, &s), "bm_ctx_last_target_stats");
+        return s;
+    }
     // bitcoin.Hash for each nonce (hash.go:11-15), on the first device
     std::vector<uint64_t> hash(std::string_view msg, const std::vector<uint64_t>& nonces) {
         std::vector<uint64_t> out(nonces.size());
