@@ -72,6 +72,13 @@ class TargetStats(ctypes.Structure):
                 ("devices", c_u32), ("reserved", c_u32)]
 
 
+BM_MAX_HITS = 1 << 22
+
+
+class HitsResult(ctypes.Structure):
+    _fields_ = [("hash", c_u64), ("nonce", c_u64), ("count", c_u64), ("stored", c_u64)]
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -144,6 +151,8 @@ def _open(path):
         "bm_search_target_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, c_u64, c_u64, c_u64, P(TargetResult)],
                                  ctypes.c_int),
         "bm_ctx_last_target_stats": ([vp, P(TargetStats)], ctypes.c_int),
+        "bm_search_hits_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, c_u64, c_u64, c_u64, P(Result),
+                                ctypes.c_size_t, P(HitsResult)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -348,6 +357,19 @@ class Context:
         check(self._lib.bm_search_target_gpu(self.handle, msg, len(msg), lower, upper, target, ctypes.byref(r)),
               "bm_search_target_gpu")
         return bool(r.found), r.hash, r.nonce
+
+    def search_hits(self, msg: bytes, lower: int, upper: int, target: int, cap: int = 4096):
+        """Every nonce of [lower, upper] whose hash is <= target ->
+        (count, hits, (min hash, its nonce)): hits is the list of
+        (hash, nonce) in ascending nonce order, or None when count > cap
+        (nothing is returned then; count is still exact).  cap = 0 only
+        counts."""
+        r = HitsResult()
+        buf = (Result * cap)() if cap > 0 else None
+        check(self._lib.bm_search_hits_gpu(self.handle, msg, len(msg), lower, upper, target, buf, cap,
+                                           ctypes.byref(r)), "bm_search_hits_gpu")
+        hits = None if r.count > cap else [(buf[i].hash, buf[i].nonce) for i in range(r.stored)]
+        return r.count, hits, (r.hash, r.nonce)
 
     def last_target_stats(self):
         """How much of the range the last search_target() handed out."""

@@ -41,6 +41,9 @@ static const void* g_search[kSearchRows][64];
 // target_kernel<P, NBV> table [nbv-1][P] (bm_search_target_gpu): the generic
 // kernel in target mode, every layout
 static const void* g_target[2][64];
+// hits_kernel<P, NBV> table [nbv-1][P] (bm_search_hits_gpu): the generic
+// kernel in hits mode, every layout
+static const void* g_hits[2][64];
 
 constexpr int kMaxInnerDigits = 2;  // S <= 100 nonces per task: small dequeue chunks, short tail
 constexpr uint32_t kNoncesPerLaneChunk = 100;  // default nonces per lane per dequeue (BTCMINER_CHUNK)
@@ -87,6 +90,10 @@ struct DeviceCtx {
     unsigned long long* d_hit = nullptr;  // target search: the lowest nonce at or below the target seen so
                                           // far (all-ones: none); an allocation, hence a line, of its own
     unsigned long long* h_hit = nullptr;  // pinned copy
+    unsigned long long* d_hcount = nullptr;  // hit enumeration: the hits counted so far (an allocation of its own)
+    unsigned long long* h_hcount = nullptr;  // pinned copy
+    Partial* d_hbuf = nullptr;               // the first hbuf_cap of them, in the order the lanes took their slots
+    size_t hbuf_cap = 0;                     // grows to the largest cap asked for
     Slot* d_slot = nullptr;    // this device's slot (reduce_partials writes its partial)
     Slot* d_gather = nullptr;  // nslots slots (allgather target)
     Slot* h_slots = nullptr;   // pinned: nslots slots, + 1 staging slot (a failed rank's status)
@@ -107,6 +114,12 @@ struct DeviceCtx {
     ncclComm_t comm = nullptr;  // multi-device ctx: ncclCommInitAll; joined rank ctx: the process group's
     std::vector<std::pair<const void*, int>> occ;  // kernel -> blocks per CU
     double wall_clock_hz = 100e6;                  // s_memrealtime rate
+};
+
+// What bm_search_hits_gpu adds to a search's launches.
+struct HitsReq {
+    uint64_t target;
+    uint64_t cap;
 };
 
 struct Launch {
@@ -287,6 +300,10 @@ extern "C" void bm_register_target_kernel(int p, int nbv, const void* fn) {
     if (p >= 0 && p < 64 && nbv >= 1 && nbv <= 2) bm::g_target[nbv - 1][p] = fn;
 }
 
+extern "C" void bm_register_hits_kernel(int p, int nbv, const void* fn) {
+    if (p >= 0 && p < 64 && nbv >= 1 && nbv <= 2) bm::g_hits[nbv - 1][p] = fn;
+}
+
 namespace bm {
 namespace {
 
@@ -327,15 +344,20 @@ int pad_fold_k(const bm_segment_t& s) {
     return (int)k;
 }
 
+enum KernelMode { kModeSearch = 0, kModeTarget = 1, kModeHits = 2 };
+
 int size_launch(bm_ctx* ctx, DeviceCtx& d, const bm_segment_t& s, uint32_t part_off, Launch& L,
-                bool target = false) {
+                KernelMode mode = kModeSearch) {
     // the folded kernel where it applies and this build registered it (an
     // A/B build may instantiate only some layouts): else the generic one,
-    // which gives the same answer.  A target search has generic kernels only.
-    const int fk = (ctx->padc && !target) ? pad_fold_k(s) : -1;
+    // which gives the same answer.  A target search and a hit enumeration
+    // have generic kernels only.
+    const int fk = (ctx->padc && mode == kModeSearch) ? pad_fold_k(s) : -1;
     const void* fn = fk >= 0 ? g_search[2 + fk][s.p] : nullptr;
     const bool padc = fn != nullptr;
-    if (!fn) fn = target ? g_target[s.nbv - 1][s.p] : g_search[s.nbv - 1][s.p];
+    if (!fn)
+        fn = mode == kModeTarget ? g_target[s.nbv - 1][s.p]
+                                 : mode == kModeHits ? g_hits[s.nbv - 1][s.p] : g_search[s.nbv - 1][s.p];
     if (!fn) return BM_EINTERNAL;
     int ms = std::max(1, std::min(s.max_inner, kMaxInnerDigits));
     // word LW holds one digit: the kernel steps the next one in word LW-1
@@ -413,6 +435,22 @@ int ensure_counters(DeviceCtx& d, size_t n) {
     return BM_OK;
 }
 
+// The device's hit buffer, at least n entries.  The old buffer goes only once
+// the new one exists, so a failed growth (BM_ENOMEM) leaves the context as it was.
+int ensure_hits(DeviceCtx& d, size_t n) {
+    if (n <= d.hbuf_cap) return BM_OK;
+    Partial* nb = nullptr;
+    const hipError_t e = hipMalloc(&nb, n * sizeof(Partial));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? BM_ENOMEM : BM_EHIP;
+    }
+    if (d.d_hbuf) (void)hipFree(d.d_hbuf);
+    d.d_hbuf = nb;
+    d.hbuf_cap = n;
+    return BM_OK;
+}
+
 int ensure_partials(DeviceCtx& d, size_t n) {
     if (n <= d.part_cap) return BM_OK;
     if (d.d_part) BM_HIP(hipFree(d.d_part));
@@ -441,6 +479,8 @@ int init_device(DeviceCtx& d, int id, int nslots) {
     BM_HIP(hipMalloc(&d.d_slot, sizeof(Slot)));
     BM_HIP(hipMalloc(&d.d_hit, 128));
     BM_HIP(hipHostMalloc(&d.h_hit, sizeof(unsigned long long), hipHostMallocDefault));
+    BM_HIP(hipMalloc(&d.d_hcount, 128));
+    BM_HIP(hipHostMalloc(&d.h_hcount, sizeof(unsigned long long), hipHostMallocDefault));
     BM_HIP(hipMalloc(&d.d_gather, sizeof(Slot) * (size_t)nslots));
     BM_HIP(hipHostMalloc(&d.h_slots, sizeof(Slot) * (size_t)(nslots + 1), hipHostMallocDefault));
     for (auto& e : d.ev) BM_HIP(hipEventCreate(&e));
@@ -474,6 +514,9 @@ void destroy_device(DeviceCtx& d) {
     if (d.d_slot) (void)hipFree(d.d_slot);
     if (d.d_hit) (void)hipFree(d.d_hit);
     if (d.h_hit) (void)hipHostFree(d.h_hit);
+    if (d.d_hcount) (void)hipFree(d.d_hcount);
+    if (d.h_hcount) (void)hipHostFree(d.h_hcount);
+    if (d.d_hbuf) (void)hipFree(d.d_hbuf);
     if (d.d_gather) (void)hipFree(d.d_gather);
     if (d.d_hash_io) (void)hipFree(d.d_hash_io);
     if (d.d_test) (void)hipFree(d.d_test);
@@ -601,8 +644,11 @@ void drain(bm_ctx* ctx) {
 // target != nullptr (bm_search_target_gpu): the target kernels, enqueued in
 // ascending nonce order so that a hit cancels what lies above it; the hit
 // word and the dequeue counters come back with the partial.
+// hits != nullptr (bm_search_hits_gpu): the hits kernels in a search's launch
+// order; the device's hit counter is zeroed before the first launch and comes
+// back with the partial.
 int enqueue_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, uint32_t& first,
-                   std::atomic<int>& enqueued, const uint64_t* target) {
+                   std::atomic<int>& enqueued, const uint64_t* target, const HitsReq* hits) {
     DeviceCtx& d = ctx->devs[di];
     const bool mark = ctx->balance || ctx->timing;  // per-device span events
     BM_HIP(hipSetDevice(d.id));
@@ -617,6 +663,10 @@ int enqueue_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, uint32_t&
     if (target) {
         *d.h_hit = ~0ull;
         BM_HIP(hipMemsetAsync(d.d_hit, 0xFF, sizeof(unsigned long long), d.stream));
+    }
+    if (hits) {
+        *d.h_hcount = 0;
+        BM_HIP(hipMemsetAsync(d.d_hcount, 0, sizeof(unsigned long long), d.stream));
     }
     // stream of each launch: biggest first (a target search: lowest nonces
     // first), round-robin over the streams
@@ -648,7 +698,9 @@ int enqueue_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, uint32_t&
         uint64_t tgt = target ? *target : 0;
         void* kargs[] = {&L.args, &d.d_part, &ctr};
         void* targs[] = {&L.args, &d.d_part, &ctr, &tgt, &d.d_hit};  // target_kernel's
-        BM_HIP(hipLaunchKernel(L.fn, dim3(L.grid), dim3(kBlock), target ? targs : kargs, 0, s));
+        uint64_t htgt = hits ? hits->target : 0, hcap = hits ? hits->cap : 0;
+        void* hargs[] = {&L.args, &d.d_part, &ctr, &htgt, &d.d_hcount, &d.d_hbuf, &hcap};  // hits_kernel's
+        BM_HIP(hipLaunchKernel(L.fn, dim3(L.grid), dim3(kBlock), target ? targs : hits ? hargs : kargs, 0, s));
         if (timed) BM_HIP(hipEventRecord(d.ev[2 * li + 1], s));
         nparts += L.grid;
     }
@@ -661,6 +713,8 @@ int enqueue_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, uint32_t&
     BM_HIP(hipGetLastError());
     if (mark) BM_HIP(hipEventRecord(d.bal[1], d.stream));
     if (target) BM_HIP(hipMemcpyAsync(d.h_hit, d.d_hit, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+    if (hits)
+        BM_HIP(hipMemcpyAsync(d.h_hcount, d.d_hcount, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
     // clock stamps, for the launch stats; a target search: the dequeue counters
     if (((BM_CLOCK_PROBE && ctx->timing) || target) && !launches.empty())
         BM_HIP(hipMemcpyAsync(d.h_ctr, d.d_ctr, launches.size() * kCtrStride * sizeof(unsigned long long),
@@ -690,13 +744,13 @@ int guarded(F&& f) noexcept {
 // skew of a serial submission; bm_stats_t.dev_start_ms reports what is left
 // of it).
 int enqueue(bm_ctx* ctx, std::vector<std::vector<Launch>>& launches, std::vector<uint32_t>& first,
-            const uint64_t* target = nullptr) {
+            const uint64_t* target = nullptr, const HitsReq* hits = nullptr) {
     const int ndev = (int)ctx->devs.size();
     if (ctx->fault_after == 0) return BM_EINTERNAL;  // test hook (also for a rank with nothing to scan)
     std::atomic<int> enqueued{0};
     ctx->stats.start_threads = 1;
     auto one = [&](int di) {
-        return guarded([&] { return enqueue_device(ctx, di, launches[di], first[di], enqueued, target); });
+        return guarded([&] { return enqueue_device(ctx, di, launches[di], first[di], enqueued, target, hits); });
     };
     if (ndev == 1) return one(0);
     std::vector<int> rc(ndev, BM_OK);
@@ -955,7 +1009,7 @@ int combine_group(bm_ctx* ctx, int own_rc, Partial* best_out) {
 // the devices (the partitioner: slot_pieces over ctx->shares; an empty piece
 // has lo > hi); plan and size every launch.
 int plan_launches(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
-                  std::vector<std::vector<Launch>>& launches, bool target = false) {
+                  std::vector<std::vector<Launch>>& launches, KernelMode mode = kModeSearch) {
     bm_stats_t& st = ctx->stats;
     const int ndev = (int)ctx->devs.size();
     uint64_t lo = lower, hi = upper;
@@ -994,7 +1048,7 @@ int plan_launches(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, u
         uint32_t off = 0;
         for (const auto& s : segs) {
             Launch L;
-            rc = size_launch(ctx, ctx->devs[di], s, off, L, target);
+            rc = size_launch(ctx, ctx->devs[di], s, off, L, mode);
             if (rc != BM_OK) return rc;
             L.stat.device = di;
             off += L.grid;
@@ -1219,7 +1273,7 @@ int target_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uin
     std::vector<std::vector<Launch>> launches(ndev);
     std::vector<uint32_t> first(ndev, 0);
     Partial best{UINT64_MAX, UINT64_MAX};
-    int rc = guarded([&] { return plan_launches(ctx, msg, len, lower, upper, launches, true); });
+    int rc = guarded([&] { return plan_launches(ctx, msg, len, lower, upper, launches, kModeTarget); });
     if (rc == BM_OK) rc = enqueue(ctx, launches, first, &target);
     if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
     if (rc == BM_OK) rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
@@ -1260,6 +1314,80 @@ int target_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uin
         *out = bm_target_result_t{host_hash(msg, len, hit), hit, 1, 0};
     else
         *out = bm_target_result_t{best.hash, best.nonce, 0, 0};
+    return BM_OK;
+}
+
+// bm_search_hits_gpu: search_impl's stages with the hits kernels, in a
+// search's launch order (a full scan).  Each device appends its hits to a
+// buffer of its own in whatever order its lanes took their slots; the host
+// reads every counter back, and only when their sum fits in cap the entries,
+// sorted by nonce per device and concatenated in device order (pieces ascend
+// with the device index).  hits and out are written last, on success only.
+int hits_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
+              bm_result_t* hits, size_t cap, bm_hits_result_t* out) {
+    const auto t_start = std::chrono::steady_clock::now();
+    bm_stats_t& st = ctx->stats;
+    std::memset(&st, 0, sizeof st);
+    record_rccl(ctx, false);
+    const int ndev = (int)ctx->devs.size();
+    if (lower > upper) {
+        stamp_common(ctx);
+        *out = bm_hits_result_t{UINT64_MAX, UINT64_MAX, 0, 0};
+        return BM_OK;
+    }
+
+    std::vector<std::vector<Launch>> launches(ndev);
+    std::vector<uint32_t> first(ndev, 0);
+    std::vector<Partial> got;
+    Partial best{UINT64_MAX, UINT64_MAX};
+    uint64_t count = 0;
+    const HitsReq req{target, (uint64_t)cap};
+    auto fail = [&](int rc) {
+        drain(ctx);
+        std::memset(&st, 0, sizeof st);
+        record_rccl(ctx, false);
+        stamp_common(ctx);
+        return rc;
+    };
+    int rc = guarded([&] { return plan_launches(ctx, msg, len, lower, upper, launches, kModeHits); });
+    for (int di = 0; di < ndev && rc == BM_OK; ++di) {
+        if (launches[di].empty()) continue;
+        DeviceCtx& d = ctx->devs[di];
+        rc = hip_status(hipSetDevice(d.id));
+        if (rc == BM_OK) rc = ensure_hits(d, std::max<size_t>(cap, 1));
+    }
+    if (rc == BM_OK) rc = enqueue(ctx, launches, first, nullptr, &req);
+    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
+    if (rc != BM_OK) return fail(rc);
+
+    for (int di = 0; di < ndev; ++di)
+        if (!launches[di].empty()) count += *ctx->devs[di].h_hcount;
+    if (count <= cap && count > 0) {
+        rc = guarded([&] {
+            got.resize((size_t)count);
+            size_t at = 0;
+            for (int di = 0; di < ndev; ++di) {
+                DeviceCtx& d = ctx->devs[di];
+                const size_t n = launches[di].empty() ? 0 : (size_t)*d.h_hcount;
+                if (n == 0) continue;
+                BM_HIP(hipSetDevice(d.id));
+                BM_HIP(hipMemcpyAsync(got.data() + at, d.d_hbuf, n * sizeof(Partial), hipMemcpyDeviceToHost, d.stream));
+                BM_HIP(hipStreamSynchronize(d.stream));
+                std::sort(got.begin() + at, got.begin() + at + n,
+                          [](const Partial& a, const Partial& b) { return a.nonce < b.nonce; });
+                at += n;
+            }
+            return (int)BM_OK;
+        });
+        if (rc != BM_OK) return fail(rc);
+    }
+    rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
+    if (rc != BM_OK) return fail(rc);
+
+    const uint64_t stored = count <= cap ? count : 0;
+    static_assert(sizeof(bm_result_t) == sizeof(Partial), "hit entry layout");
+    if (stored) std::memcpy(hits, got.data(), (size_t)stored * sizeof(Partial));
+    *out = bm_hits_result_t{best.hash, best.nonce, count, stored};
     return BM_OK;
 }
 
@@ -1627,6 +1755,18 @@ int bm_search_target_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t
     bm::DeviceGuard guard;
     bm_target_result_t r;
     int rc = bm::guarded([&] { return bm::target_impl(ctx, msg, len, lower, upper, target, &r); });
+    if (rc == BM_OK) *out = r;
+    return rc;
+}
+
+int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                       uint64_t target, bm_result_t* hits, size_t cap, bm_hits_result_t* out) {
+    if (!ctx || !out || (len && !msg) || len > BM_MAX_MSG_LEN) return BM_EINVAL;
+    if (cap > BM_MAX_HITS || (!hits && cap > 0)) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // the group's allgather slot carries no hits
+    bm::DeviceGuard guard;
+    bm_hits_result_t r;
+    int rc = bm::guarded([&] { return bm::hits_impl(ctx, msg, len, lower, upper, target, hits, cap, &r); });
     if (rc == BM_OK) *out = r;
     return rc;
 }

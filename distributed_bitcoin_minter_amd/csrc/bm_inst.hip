@@ -18,8 +18,12 @@
 // BM_INST_TARGET: this unit instantiates ONLY target_kernel<P, NBV> (the
 // Makefile's instt1_* / instt2_* units), registered into a table of its own.
 
+// BM_INST_HITS: this unit instantiates ONLY hits_kernel<P, NBV> (the
+// Makefile's insth1_* / insth2_* units), registered into a table of its own.
+
 extern "C" void bm_register_search_kernel(int p, int nbv, const void* fn);
 extern "C" void bm_register_target_kernel(int p, int nbv, const void* fn);
+extern "C" void bm_register_hits_kernel(int p, int nbv, const void* fn);
 
 #include <utility>
 
@@ -32,6 +36,11 @@ namespace {
 template <int P>
 void register_one() {
     bm_register_target_kernel(P, BM_INST_NBV, reinterpret_cast<const void*>(&bm::target_kernel<P, BM_INST_NBV>));
+}
+#elif defined(BM_INST_HITS)
+template <int P>
+void register_one() {
+    bm_register_hits_kernel(P, BM_INST_NBV, reinterpret_cast<const void*>(&bm::hits_kernel<P, BM_INST_NBV>));
 }
 #elif defined(BM_INST_PADK_LO)
 template <int P, int K>

@@ -388,10 +388,27 @@ constexpr int kClockSlot = 16;
 //    nonces strictly above a recorded hit are ever skipped and the word only
 //    decreases, so the smallest hit is always hashed and recorded, whenever
 //    each wave happens to see the word.  Nothing waits on another wave.
-template <int P, int NBV, int PADK, bool TGT = false>
+//
+// HITS (hits_kernel): besides the running minimum, every nonce of the launch's
+// range whose hash is <= target, appended to hit_buf through the counter
+// `hit` (one word per device and call, zero before the first launch):
+//  * no new per-nonce work: the one 32-bit compare is against
+//    max(bh, target >> 32), kept in bh's register and updated only on the
+//    rare path.  Every hit has h0 <= target >> 32, so every hit takes the
+//    rare branch; the minimum's own test there is the exact 64-bit one, so
+//    the extra entries change nothing for it.
+//  * on the rare path the exact h <= target and the range check (tasks
+//    over-cover their launch) decide; a hit takes the next index with one
+//    atomicAdd and, below hit_cap, writes its (hash, nonce) there with one
+//    16-byte store.  The slot is that lane's alone.  The counter goes on
+//    counting past hit_cap, so the count is exact whatever the buffer holds.
+//  * a full scan: no wave reads the counter, nothing leaves early.
+template <int P, int NBV, int PADK, bool TGT = false, bool HITS = false>
 BM_DEV void search_body(const SearchArgs& A, Partial* __restrict__ part, unsigned long long* __restrict__ counter,
-                        uint64_t target = 0, unsigned long long* hit = nullptr) {
-    static_assert(!TGT || PADK == -1, "target mode runs the generic kernels");
+                        uint64_t target = 0, unsigned long long* hit = nullptr, Partial* hit_buf = nullptr,
+                        uint64_t hit_cap = 0) {
+    static_assert(!(TGT || HITS) || PADK == -1, "target and hits modes run the generic kernels");
+    static_assert(!(TGT && HITS), "one mode");
     static_assert(P >= 0 && P < 64 && (NBV == 1 || (NBV == 2 && P <= 18)), "layout");
     constexpr int LW = P / 4;                      // last-block word holding the last digit
     constexpr int BOFF = 16 * (NBV - 1);           // word offset of the last block
@@ -420,7 +437,9 @@ BM_DEV void search_body(const SearchArgs& A, Partial* __restrict__ part, unsigne
     constexpr uint32_t inc3 = (P % 4) >= 3 ? 1u << (8 * (6 - P % 4)) : 0u;
 
     uint64_t best_h = ~0ull, best_n = ~0ull;
-    uint32_t bh = 0xFFFFFFFFu;  // high word of best_h
+    uint32_t bh = 0xFFFFFFFFu;  // high word of best_h (HITS: never below the target's)
+    const uint32_t thi = (uint32_t)(target >> 32);
+    (void)thi;
 #if BM_LDS_BEST
     // The full 64-bit best and its nonce are touched only on the rare path
     // (a new low); in LDS they cost no VGPRs, so no spill slots and no scratch
@@ -572,17 +591,26 @@ BM_DEV void search_body(const SearchArgs& A, Partial* __restrict__ part, unsigne
                             if (h <= target && v >= A.vlo && v <= A.vhi)
                                 atomicMin(hit, (unsigned long long)(A.nonce_base + v));
                         }
+                        if constexpr (HITS) {
+                            if (h <= target && v >= A.vlo && v <= A.vhi) {
+                                const unsigned long long idx = atomicAdd(hit, 1ull);
+                                if (idx < hit_cap) {
+                                    using u64x2 = unsigned long long __attribute__((ext_vector_type(2)));
+                                    *reinterpret_cast<u64x2*>(hit_buf + idx) = u64x2{h, A.nonce_base + v};
+                                }
+                            }
+                        }
 #if BM_LDS_BEST
                         if (h < lbest_h[threadIdx.x] && v >= A.vlo && v <= A.vhi) {
                             lbest_h[threadIdx.x] = h;
                             lbest_n[threadIdx.x] = A.nonce_base + v;
-                            bh = h0;
+                            bh = HITS ? (h0 > thi ? h0 : thi) : h0;
                         }
 #else
                         if (h < best_h && v >= A.vlo && v <= A.vhi) {
                             best_h = h;
                             best_n = A.nonce_base + v;
-                            bh = h0;
+                            bh = HITS ? (h0 > thi ? h0 : thi) : h0;
                         }
 #endif
                     }
@@ -654,6 +682,16 @@ __global__ __launch_bounds__(kBlock) BM_KATTR void target_kernel(
     const SearchArgs A, Partial* __restrict__ part, unsigned long long* __restrict__ counter, const uint64_t target,
     unsigned long long* __restrict__ hit) {
     search_body<P, NBV, -1, true>(A, part, counter, target, hit);
+}
+
+// The generic kernel in hits mode (search_body's HITS), for every layout, the
+// padding-block ones included.  Occupancy request as for search_kernel.
+// hit_buf holds hit_cap entries of 16 bytes, 16-byte aligned.
+template <int P, int NBV>
+__global__ __launch_bounds__(kBlock) BM_KATTR void hits_kernel(
+    const SearchArgs A, Partial* __restrict__ part, unsigned long long* __restrict__ counter, const uint64_t target,
+    unsigned long long* __restrict__ hit_count, Partial* __restrict__ hit_buf, const uint64_t hit_cap) {
+    search_body<P, NBV, -1, false, true>(A, part, counter, target, hit_count, hit_buf, hit_cap);
 }
 
 }  // namespace bm

@@ -190,6 +190,44 @@ typedef struct bm_target_result {
 int bm_search_target_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
                          uint64_t target, bm_target_result_t* out);
 
+/* ---- hit enumeration: every nonce whose hash meets a target --------------
+ * bm_search_hits_gpu scans all of [lower, upper] (no early exit) and returns
+ * every n with Hash(msg, n) <= target (full 64-bit unsigned compare), plus
+ * the range's minimum.
+ *   hits[0 .. stored) holds {Hash(msg, n), n} for every hit in ascending nonce
+ *     order, each exactly once.  count is exact, always.
+ *   All or nothing: count > cap writes NOTHING to hits, stored = 0, and the
+ *     call still succeeds with the exact count; ask again with a larger buffer
+ *     or a smaller range.  No subset is ever returned, so the result never
+ *     depends on timing, residency, streams, task digits, max_windows or the
+ *     split.
+ *   hits == NULL with cap == 0 is a pure count.  cap > BM_MAX_HITS, or
+ *     hits == NULL with cap > 0: BM_EINVAL.
+ *   lower > upper: {2^64-1, 2^64-1, 0, 0}.  upper = 2^64-1 is legal and the
+ *     nonce 2^64-1 is reported like any other.
+ * On failure `out` and `hits` are untouched and the context stays usable (a
+ * device buffer that cannot grow to cap: BM_ENOMEM).
+ * Contexts: one device, or one process over several devices (a device listed
+ * N times included): each device appends to a buffer and a counter of its
+ * own, and the host concatenates them in device order (pieces ascend) --
+ * always by host copies.  A rank context with world > 1 returns BM_EINVAL.
+ * bm_ctx_set_balance does not learn from these calls (their time depends on
+ * the hit density); bm_ctx_set_test_fault applies as for a search;
+ * bm_ctx_last_stats is filled as for a search (nonces = the range size).
+ * Cost: that of bm_search_gpu while hits are rare.  Every hit is one atomic
+ * on one word per device, so targets of about 8 leading zero bits or fewer
+ * are bound by that atomic, not by hashing; the result stays exact at any
+ * density, target = 2^64-1 included. */
+#define BM_MAX_HITS (1u << 22) /* entries; 64 MiB of device buffer per device at most */
+typedef struct bm_hits_result {
+    uint64_t hash, nonce; /* the range's minimum: exactly bm_search_gpu's answer */
+    uint64_t count;       /* nonces n in [lower, upper] with Hash(msg, n) <= target: exact, always */
+    uint64_t stored;      /* entries written to hits[]: count when count <= cap, else 0 */
+} bm_hits_result_t;
+
+int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                       uint64_t target, bm_result_t* hits, size_t cap, bm_hits_result_t* out);
+
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */
 int bm_hash_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,

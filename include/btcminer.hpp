@@ -114,6 +114,20 @@ class Context {
               "bm_search_target_gpu");
         return r;
     }
+    // every n in [lower, upper] with Hash(msg, n) <= target, ascending, into
+    // `hits` (resized to the result's `stored`: empty when count > cap), plus
+    // the exact count and the range's minimum: bm_search_hits_gpu
+    bm_hits_result_t search_hits(std::string_view msg, uint64_t lower, uint64_t upper, uint64_t target,
+                                 std::vector<bm_result_t>& hits, size_t cap) {
+        bm_hits_result_t r;
+        std::vector<bm_result_t> buf(cap);
+        check(bm_search_hits_gpu(ctx_, reinterpret_cast<const uint8_t*>(msg.data()), msg.size(), lower, upper, target,
+                                 cap ? buf.data() : nullptr, cap, &r),
+              "bm_search_hits_gpu");
+        buf.resize(static_cast<size_t>(r.stored));
+        hits = std::move(buf);
+        return r;
+    }
     bm_target_stats_t last_target_stats() const {
         bm_target_stats_t s;
         check(bm_ctx_last_target_stats(ctx_, &s), "bm_ctx_last_target_stats");
