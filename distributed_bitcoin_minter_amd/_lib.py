@@ -79,6 +79,16 @@ class HitsResult(ctypes.Structure):
     _fields_ = [("hash", c_u64), ("nonce", c_u64), ("count", c_u64), ("stored", c_u64)]
 
 
+class HeaderResult(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("nonce", c_u32), ("found", c_i32)]
+
+
+HEADER_BYTES = 80
+U32_MAX = (1 << 32) - 1
+U256_MAX = (1 << 256) - 1
+BM_MAX_HEADER_HASHES = 1 << 24
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -153,6 +163,9 @@ def _open(path):
         "bm_ctx_last_target_stats": ([vp, P(TargetStats)], ctypes.c_int),
         "bm_search_hits_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, c_u64, c_u64, c_u64, P(Result),
                                 ctypes.c_size_t, P(HitsResult)], ctypes.c_int),
+        "bm_search_header_gpu": ([vp, ctypes.c_char_p, c_u32, c_u32, ctypes.c_char_p, P(HeaderResult)], ctypes.c_int),
+        "bm_header_hash_gpu": ([vp, ctypes.c_char_p, P(c_u32), ctypes.c_size_t, P(ctypes.c_uint8)], ctypes.c_int),
+        "bm_header_target_from_bits": ([c_u32, P(ctypes.c_uint8)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -230,6 +243,36 @@ def split_range(lower: int, upper: int, n: int, shares=None):
     sh = (ctypes.c_uint32 * n)(*shares) if shares is not None else None
     check(load().bm_split_range(lower, upper, sh, n, lo, hi), "bm_split_range")
     return [(a, b) if a <= b else None for a, b in zip(lo, hi)]
+
+
+def bits_to_target(nbits: int) -> int:
+    """Bitcoin's compact target (a block header's `bits` field) as an integer
+    (bm_header_target_from_bits, pure CPU); ValueError for a negative or
+    overflowing form."""
+    if not 0 <= nbits <= U32_MAX:
+        raise ValueError(f"bits must be in 0..2^32-1, got {nbits}")
+    buf = (ctypes.c_uint8 * 32)()
+    if load().bm_header_target_from_bits(nbits, buf) != BM_OK:
+        raise ValueError(f"bits {nbits:#010x} is negative or overflows 256 bits")
+    return int.from_bytes(bytes(buf), "big")
+
+
+def _header_bytes(header) -> bytes:
+    header = bytes(header)
+    if len(header) != HEADER_BYTES:
+        raise ValueError(f"a block header is {HEADER_BYTES} bytes, got {len(header)}")
+    return header
+
+
+def _target_bytes(target) -> bytes:
+    """A target as 32 bytes, most significant first, from an int or 32 bytes."""
+    if isinstance(target, int) and not isinstance(target, bool):
+        if not 0 <= target <= U256_MAX:
+            raise ValueError("target must be in 0..2^256-1")
+        return target.to_bytes(32, "big")
+    if isinstance(target, (bytes, bytearray)) and len(target) == 32:
+        return bytes(target)
+    raise ValueError("target must be an int in 0..2^256-1 or 32 bytes (most significant first)")
 
 
 def rccl_unique_id() -> bytes:
@@ -376,6 +419,37 @@ class Context:
         s = TargetStats()
         check(self._lib.bm_ctx_last_target_stats(self.handle, ctypes.byref(s)), "bm_ctx_last_target_stats")
         return s
+
+    def search_header(self, header: bytes, nonce_lo: int = 0, nonce_hi: int = U32_MAX, target=U256_MAX):
+        """Bitcoin block header: the first nonce of [nonce_lo, nonce_hi] whose
+        double SHA-256 (as a little-endian 256-bit integer) is <= target ->
+        (True, hash, nonce); none -> (False, hash, nonce) of the range's best
+        share, the minimum of (hash >> 192, nonce).  target: an int or 32 bytes,
+        most significant first.  An empty range gives (False, 2^256-1, 2^32-1)."""
+        header = _header_bytes(header)
+        for v, what in ((nonce_lo, "nonce_lo"), (nonce_hi, "nonce_hi")):
+            if not isinstance(v, int) or not 0 <= v <= U32_MAX:
+                raise ValueError(f"{what} must be in 0..2^32-1, got {v!r}")
+        tgt = _target_bytes(target)
+        r = HeaderResult()
+        check(self._lib.bm_search_header_gpu(self.handle, header, nonce_lo, nonce_hi, tgt, ctypes.byref(r)),
+              "bm_search_header_gpu")
+        return bool(r.found), int.from_bytes(bytes(r.hash), "big"), r.nonce
+
+    def header_hash_many(self, header: bytes, nonces):
+        """The header's double SHA-256 under each nonce, as integers (the
+        digest read little-endian), on the first device."""
+        header = _header_bytes(header)
+        nonces = list(nonces)
+        for v in nonces:
+            if not 0 <= v <= U32_MAX:
+                raise ValueError(f"a nonce must be in 0..2^32-1, got {v!r}")
+        n = len(nonces)
+        arr = (c_u32 * max(n, 1))(*nonces)
+        out = (ctypes.c_uint8 * (32 * max(n, 1)))()
+        check(self._lib.bm_header_hash_gpu(self.handle, header, arr, n, out), "bm_header_hash_gpu")
+        raw = bytes(out)
+        return [int.from_bytes(raw[32 * i:32 * i + 32], "big") for i in range(n)]
 
     def hash_many(self, msg: bytes, nonces):
         n = len(nonces)

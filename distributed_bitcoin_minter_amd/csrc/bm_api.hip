@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "bm_aux_kernels.hpp"
+#include "bm_header.hpp"
 #include "bm_plan.hpp"
 #include "btcminer.h"
 
@@ -44,6 +45,10 @@ static const void* g_target[2][64];
 // hits_kernel<P, NBV> table [nbv-1][P] (bm_search_hits_gpu): the generic
 // kernel in hits mode, every layout
 static const void* g_hits[2][64];
+// header_kernel and header_hash_kernel (bm_search_header_gpu, bm_header_hash_gpu),
+// filled by bm_header_inst.hip at load time
+static const void* g_header_search = nullptr;
+static const void* g_header_hash = nullptr;
 
 constexpr int kMaxInnerDigits = 2;  // S <= 100 nonces per task: small dequeue chunks, short tail
 constexpr uint32_t kNoncesPerLaneChunk = 100;  // default nonces per lane per dequeue (BTCMINER_CHUNK)
@@ -102,6 +107,8 @@ struct DeviceCtx {
     size_t test_cap = 0;
     uint64_t* d_hash_io = nullptr;
     size_t hash_cap = 0;
+    uint32_t* d_hdr_io = nullptr;  // bm_header_hash_gpu: n nonces, then 8 digest words per nonce
+    size_t hdr_cap = 0;
     hipEvent_t ev[2 * kEventPairs] = {};
     hipStream_t aux[kMaxStreams - 1] = {};  // extra launch streams (ctx->streams > 1)
     hipEvent_t fork = nullptr, join[kMaxStreams - 1] = {};
@@ -302,6 +309,11 @@ extern "C" void bm_register_target_kernel(int p, int nbv, const void* fn) {
 
 extern "C" void bm_register_hits_kernel(int p, int nbv, const void* fn) {
     if (p >= 0 && p < 64 && nbv >= 1 && nbv <= 2) bm::g_hits[nbv - 1][p] = fn;
+}
+
+extern "C" void bm_register_header_kernels(const void* search_fn, const void* hash_fn) {
+    bm::g_header_search = search_fn;
+    bm::g_header_hash = hash_fn;
 }
 
 namespace bm {
@@ -519,6 +531,7 @@ void destroy_device(DeviceCtx& d) {
     if (d.d_hbuf) (void)hipFree(d.d_hbuf);
     if (d.d_gather) (void)hipFree(d.d_gather);
     if (d.d_hash_io) (void)hipFree(d.d_hash_io);
+    if (d.d_hdr_io) (void)hipFree(d.d_hdr_io);
     if (d.d_test) (void)hipFree(d.d_test);
     if (d.h_slots) (void)hipHostFree(d.h_slots);
     if (d.own_done) (void)hipEventDestroy(d.own_done);
@@ -1467,6 +1480,210 @@ int hash_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* nonce
     return BM_OK;
 }
 
+
+// ---- block-header search (bm_search_header_gpu) ---------------------------
+
+// One device's launch of header_kernel: its piece of the nonce range in tasks
+// of 256 nonces, chunks of 64 * m tasks per dequeue, at most one resident grid.
+void size_header_launch(bm_ctx* ctx, DeviceCtx& d, const HeaderArgs& base, uint32_t lo, uint32_t hi, HeaderArgs& A,
+                        Launch& L) {
+    A = base;
+    A.lo = lo;
+    A.hi = hi;
+    A.t0 = lo >> kHeaderTaskBits;
+    const uint64_t T = (uint64_t)(hi >> kHeaderTaskBits) - A.t0 + 1;
+    A.ntask = (uint32_t)T;
+    const uint64_t resident = (uint64_t)blocks_per_cu(ctx, d, g_header_search) * (uint64_t)d.cus;
+    const uint64_t m_max = std::max<uint64_t>(1, ctx->lane_chunk / kHeaderTaskNonces);
+    const uint32_t m =
+        (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(m_max, T / (8 * resident * (uint64_t)kBlock)));
+    const uint64_t chunks = (T + 64ull * m - 1) / (64ull * m);
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((chunks + 3) / 4, resident));
+    A.chunk_m = m;
+    A.part_off = 0;
+    std::memset(&L, 0, sizeof L);
+    L.fn = g_header_search;
+    L.grid = (uint32_t)grid;
+    L.stat.nbv = 1;
+    L.stat.inner_digits = 0;
+    L.stat.nonces = (uint64_t)hi - lo + 1;
+    L.stat.grid = (uint32_t)grid;
+    L.stat.tasks_per_thread = (uint32_t)((chunks + grid * 4 - 1) / (grid * 4) * m);
+}
+
+// One device's work of a header search: its launch (none for an empty piece)
+// and the second-pass reduction; the hit word and the dequeue counter come
+// back with the partial (combine_local's host copies).
+int enqueue_header_device(bm_ctx* ctx, int di, std::vector<Launch>& launches, HeaderArgs& A,
+                          std::atomic<int>& enqueued) {
+    DeviceCtx& d = ctx->devs[di];
+    const bool mark = ctx->balance || ctx->timing;
+    BM_HIP(hipSetDevice(d.id));
+    if (d.test_delay_us > 0) std::this_thread::sleep_for(std::chrono::microseconds(d.test_delay_us));
+    if (mark) BM_HIP(hipEventRecord(d.bal[0], d.stream));
+    d.submitted = std::chrono::steady_clock::now();
+    uint32_t nparts = 0;
+    *d.h_hit = ~0ull;
+    if (!launches.empty()) {
+        Launch& L = launches[0];
+        BM_HIP(hipMemsetAsync(d.d_ctr, 0, kCtrStride * sizeof(unsigned long long), d.stream));
+        BM_HIP(hipMemsetAsync(d.d_hit, 0xFF, sizeof(unsigned long long), d.stream));
+        if (ctx->fault_after >= 0 && enqueued.fetch_add(1) >= ctx->fault_after) return BM_EINTERNAL;  // test hook
+        if (ctx->timing) BM_HIP(hipEventRecord(d.ev[0], d.stream));
+        unsigned long long* ctr = d.d_ctr;
+        void* args[] = {&A, &d.d_part, &ctr, &d.d_hit};
+        BM_HIP(hipLaunchKernel(L.fn, dim3(L.grid), dim3(kBlock), args, 0, d.stream));
+        if (ctx->timing) BM_HIP(hipEventRecord(d.ev[1], d.stream));
+        nparts = L.grid;
+    }
+    reduce_partials<<<1, kReduceThreads, 0, d.stream>>>(d.d_part, nparts, &d.d_slot->p);
+    BM_HIP(hipGetLastError());
+    if (mark) BM_HIP(hipEventRecord(d.bal[1], d.stream));
+    if (!launches.empty()) {
+        BM_HIP(hipMemcpyAsync(d.h_hit, d.d_hit, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+        BM_HIP(hipMemcpyAsync(d.h_ctr, d.d_ctr, kCtrStride * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              d.stream));
+    }
+    return BM_OK;
+}
+
+// bm_search_header_gpu: the nonce range cut over the devices by the
+// partitioner, one launch and one hit word per device; the host takes the
+// lowest-nonce hit (pieces ascend with the device index), or else the
+// lexicographic min of the (top 64 bits, nonce) partials, and recomputes the
+// full 256-bit hash of the one nonce it returns.  Always host copies.
+int header_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, const uint8_t* target,
+                bm_header_result_t* out) {
+    const auto t_start = std::chrono::steady_clock::now();
+    bm_stats_t& st = ctx->stats;
+    bm_target_stats_t& ts = ctx->tstats;
+    std::memset(&st, 0, sizeof st);
+    std::memset(&ts, 0, sizeof ts);
+    record_rccl(ctx, false);
+    const int ndev = (int)ctx->devs.size();
+    if (lo > hi) {
+        stamp_common(ctx);
+        std::memset(out->hash, 0xFF, sizeof out->hash);
+        out->nonce = 0xFFFFFFFFu;
+        out->found = 0;
+        return BM_OK;
+    }
+    if (!g_header_search) return BM_EINTERNAL;
+
+    HeaderArgs base;
+    std::memset(&base, 0, sizeof base);
+    host::header_precompute(header, base);
+    for (int i = 0; i < 8; ++i) base.tgt[i] = host::load_be32(target + 4 * i);
+
+    auto fail = [&](int rc) {
+        drain(ctx);
+        std::memset(&st, 0, sizeof st);
+        record_rccl(ctx, false);
+        stamp_common(ctx);
+        return rc;
+    };
+    std::vector<std::vector<Launch>> launches(ndev);
+    std::vector<HeaderArgs> args(ndev);
+    std::vector<uint32_t> first(ndev, 0);
+    st.nonces = (uint64_t)hi - lo + 1;
+    const std::vector<Piece> pieces =
+        slot_pieces(lo, hi, ndev, ctx->rank_ctx ? std::vector<uint32_t>() : ctx->shares);
+    for (int di = 0; di < ndev; ++di) {
+        DeviceCtx& d = ctx->devs[di];
+        d.piece_nonces = pieces[di].lo <= pieces[di].hi ? pieces[di].hi - pieces[di].lo + 1 : 0;
+        if (pieces[di].lo > pieces[di].hi) continue;
+        BM_HIP(hipSetDevice(d.id));
+        Launch L;
+        size_header_launch(ctx, d, base, (uint32_t)pieces[di].lo, (uint32_t)pieces[di].hi, args[di], L);
+        L.stat.device = di;
+        launches[di].push_back(L);
+        int rc = ensure_partials(d, L.grid);
+        if (rc == BM_OK) rc = ensure_counters(d, 1);
+        if (rc != BM_OK) return fail(rc);
+    }
+
+    if (ctx->fault_after == 0) return fail(BM_EINTERNAL);  // test hook
+    std::atomic<int> enqueued{0};
+    ctx->stats.start_threads = 1;
+    int rc = BM_OK;
+    for (int di = 0; di < ndev && rc == BM_OK; ++di) rc = enqueue_header_device(ctx, di, launches[di], args[di], enqueued);
+    Partial best{UINT64_MAX, UINT64_MAX};
+    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
+    if (rc == BM_OK) rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
+    if (rc != BM_OK) return fail(rc);
+
+    uint64_t hit = UINT64_MAX;
+    ts.devices = (uint32_t)std::min(ndev, BM_MAX_STAT_DEVICES);
+    for (int di = 0; di < ndev; ++di) {
+        DeviceCtx& d = ctx->devs[di];
+        if (launches[di].empty()) continue;
+        if (*d.h_hit != UINT64_MAX && hit == UINT64_MAX) hit = *d.h_hit;
+        const uint64_t tasks = std::min<uint64_t>(d.h_ctr[0], args[di].ntask);
+        const uint64_t disp = std::min<uint64_t>(tasks * kHeaderTaskNonces, launches[di][0].stat.nonces);
+        if (di < BM_MAX_STAT_DEVICES) ts.dev_dispatched[di] = disp;
+        ts.nonces_dispatched += disp;
+    }
+    const bool found = hit != UINT64_MAX;
+    const uint64_t n = found ? hit : best.nonce;
+    if (n > 0xFFFFFFFFull) return fail(BM_EINTERNAL);  // a non-empty range always has a minimum
+    bm_header_result_t r;
+    host::header_hash_msb(header, (uint32_t)n, r.hash);
+    r.nonce = (uint32_t)n;
+    r.found = found ? 1 : 0;
+    // the device's claim against the host's hash of that nonce
+    const bool meets = std::memcmp(r.hash, target, 32) <= 0;
+    uint64_t top = 0;
+    for (int i = 0; i < 8; ++i) top = (top << 8) | r.hash[i];
+    if (found ? !meets : (meets || top != best.hash)) return fail(BM_EINTERNAL);
+    *out = r;
+    return BM_OK;
+}
+
+// bm_header_hash_gpu: the full double hash of arbitrary nonces on the first
+// device, most significant byte first.
+int header_hash_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* nonces, size_t n, uint8_t* out) {
+    if (n == 0) return BM_OK;
+    if (!g_header_hash) return BM_EINTERNAL;
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    HeaderHashArgs A;
+    std::memset(&A, 0, sizeof A);
+    uint32_t st[8];
+    for (int i = 0; i < 8; ++i) st[i] = kIV256[i];
+    host::compress_bytes(st, header);
+    std::memcpy(A.mid, st, sizeof st);
+    for (int i = 0; i < 3; ++i) A.w[i] = host::load_be32(header + 64 + 4 * i);
+    A.n = (uint32_t)n;
+    if (n > d.hdr_cap) {
+        if (d.d_hdr_io) BM_HIP(hipFree(d.d_hdr_io));
+        d.d_hdr_io = nullptr;
+        d.hdr_cap = 0;
+        BM_HIP(hipMalloc(&d.d_hdr_io, 9 * n * sizeof(uint32_t)));
+        d.hdr_cap = n;
+    }
+    std::vector<uint32_t> words(8 * n);
+    uint32_t* d_in = d.d_hdr_io;
+    uint32_t* d_out = d.d_hdr_io + n;
+    BM_HIP(hipMemcpyAsync(d_in, nonces, n * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    const uint32_t grid = (uint32_t)((n + 63) / 64);
+    void* args[] = {&A, &d_in, &d_out};
+    BM_HIP(hipLaunchKernel(g_header_hash, dim3(grid), dim3(64), args, 0, d.stream));
+    BM_HIP(hipMemcpyAsync(words.data(), d_out, 8 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    // digest word k (big-endian) holds digest bytes 4k..4k+3; the hash is the
+    // digest reversed
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t w = words[8 * i + k];
+            uint8_t* o = out + 32 * i + 4 * (7 - k);
+            o[0] = (uint8_t)w;
+            o[1] = (uint8_t)(w >> 8);
+            o[2] = (uint8_t)(w >> 16);
+            o[3] = (uint8_t)(w >> 24);
+        }
+    return BM_OK;
+}
+
 }  // namespace
 }  // namespace bm
 
@@ -1769,6 +1986,31 @@ int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t l
     int rc = bm::guarded([&] { return bm::hits_impl(ctx, msg, len, lower, upper, target, hits, cap, &r); });
     if (rc == BM_OK) *out = r;
     return rc;
+}
+
+int bm_search_header_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t nonce_lo, uint32_t nonce_hi,
+                         const uint8_t* target, bm_header_result_t* out) {
+    if (!ctx || !header || !target || !out) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    bm::DeviceGuard guard;
+    bm_header_result_t r;
+    int rc = bm::guarded([&] { return bm::header_impl(ctx, header, nonce_lo, nonce_hi, target, &r); });
+    if (rc == BM_OK) *out = r;
+    return rc;
+}
+
+int bm_header_hash_gpu(bm_ctx_t* ctx, const uint8_t* header, const uint32_t* nonces, size_t n, uint8_t* out) {
+    if (!ctx || !header || (n && (!nonces || !out)) || n > BM_MAX_HEADER_HASHES) return BM_EINVAL;
+    bm::DeviceGuard guard;
+    return bm::guarded([&] { return bm::header_hash_impl(ctx, header, nonces, n, out); });
+}
+
+int bm_header_target_from_bits(uint32_t nbits, uint8_t* target) {
+    if (!target) return BM_EINVAL;
+    uint8_t t[32];
+    if (!bm::host::target_from_bits(nbits, t)) return BM_EINVAL;
+    std::memcpy(target, t, sizeof t);
+    return BM_OK;
 }
 
 int bm_ctx_last_target_stats(const bm_ctx_t* ctx, bm_target_stats_t* out) {

@@ -228,6 +228,63 @@ typedef struct bm_hits_result {
 int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
                        uint64_t target, bm_result_t* hits, size_t cap, bm_hits_result_t* out);
 
+/* ---- Bitcoin block headers: double SHA-256 over a nonce range ------------
+ * The hash of a nonce is H(n) = SHA256(SHA256(header[0:76] || le32(n))) read as
+ * a little-endian 256-bit integer (what block explorers print).  Bytes 76..79
+ * of the caller's header are ignored.  `hash` and `target` are 256-bit numbers
+ * written MOST significant byte first (= the sha256d digest bytes reversed).
+ *
+ * bm_search_header_gpu scans [nonce_lo, nonce_hi] for H(n) <= target, compared
+ * over the full 256 bits, and stops handing out work above a hit once one is
+ * known (as bm_search_target_gpu does).
+ *   found = 1: nonce is the SMALLEST n of the range with H(n) <= target and
+ *     hash = H(nonce).
+ *   found = 0: the whole range was scanned; nonce minimises the pair
+ *     (H(n) >> 192, n) lexicographically -- the top 64 bits of the hash, the
+ *     smallest nonce on equal top bits: the range's "best share" -- and
+ *     hash = H(nonce) in full (recomputed on the host).
+ *   nonce_lo > nonce_hi: found = 0, hash all 0xFF, nonce = 0xFFFFFFFF.
+ *     nonce_hi = 2^32-1 is legal.  An all-ones target always finds nonce_lo.
+ * The result never depends on timing, residency, streams, BTCMINER_CHUNK,
+ * blocks per CU or the split.  On failure `out` is untouched and the context
+ * stays usable; the next bm_search_gpu on it is unaffected.
+ * Contexts: one device, or one process over several devices (a device listed
+ * N times included): the nonce range is cut by the partitioner, each device
+ * has a hit word of its own, and the host takes the lowest-nonce hit, or else
+ * the lexicographic minimum of the partials -- always by host copies.  A rank
+ * context with world > 1 returns BM_EINVAL.
+ * bm_ctx_set_balance does not learn from these calls; bm_ctx_set_test_fault
+ * applies as for a search; bm_ctx_last_stats is filled, one launch per device
+ * (p = digits = inner_digits = 0: a launch of header_kernel);
+ * bm_ctx_last_target_stats is filled with the nonces dispatched, as for a
+ * target search.
+ *
+ * bm_header_hash_gpu: out[32*i .. 32*i+31] = H(nonces[i]), most significant
+ * byte first, on the first device of ctx, by a kernel that shares none of the
+ * search's shortcuts (the twin of bm_hash_gpu).  n <= BM_MAX_HEADER_HASHES.
+ *
+ * bm_header_target_from_bits (pure CPU): Bitcoin's compact target.
+ * mantissa = nbits & 0x7fffff, exponent = nbits >> 24, target = mantissa <<
+ * 8 * (exponent - 3), a right shift for exponents below 3.  BM_EINVAL when the
+ * sign bit 0x00800000 is set or the value overflows 256 bits.
+ *
+ * Out of scope: rolling ntime or an extranonce past 2^32 nonces (the caller
+ * changes the header and calls again; a call is a fraction of a second); hit
+ * enumeration for headers; cancelling one device's work on another device's
+ * hit; rank groups; the LSP server protocol. */
+#define BM_MAX_HEADER_HASHES (1u << 24)
+typedef struct bm_header_result {
+    uint8_t hash[32]; /* found: H(nonce); else H of the best share's nonce */
+    uint32_t nonce;
+    int32_t found;    /* 1: some nonce of the range has H <= target */
+} bm_header_result_t; /* 40 bytes */
+
+int bm_search_header_gpu(bm_ctx_t* ctx, const uint8_t header[80], uint32_t nonce_lo, uint32_t nonce_hi,
+                         const uint8_t target[32], bm_header_result_t* out);
+int bm_header_hash_gpu(bm_ctx_t* ctx, const uint8_t header[80], const uint32_t* nonces, size_t n,
+                       uint8_t* out /* 32 * n */);
+int bm_header_target_from_bits(uint32_t nbits, uint8_t target[32]);
+
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */
 int bm_hash_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,

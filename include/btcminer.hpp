@@ -133,6 +133,22 @@ class Context {
         check(bm_ctx_last_target_stats(ctx_, &s), "bm_ctx_last_target_stats");
         return s;
     }
+    // Bitcoin block header: the first nonce of [nonce_lo, nonce_hi] whose double
+    // SHA-256 is <= target (found = 1), or the range's best share (found = 0).
+    // header is 80 bytes, target 32 bytes most significant first: bm_search_header_gpu
+    bm_header_result_t search_header(const uint8_t header[80], uint32_t nonce_lo, uint32_t nonce_hi,
+                                     const uint8_t target[32]) {
+        bm_header_result_t r;
+        check(bm_search_header_gpu(ctx_, header, nonce_lo, nonce_hi, target, &r), "bm_search_header_gpu");
+        return r;
+    }
+    // the double SHA-256 of the header under each nonce, 32 bytes each, most
+    // significant byte first, on the first device: bm_header_hash_gpu
+    std::vector<uint8_t> header_hash(const uint8_t header[80], const std::vector<uint32_t>& nonces) {
+        std::vector<uint8_t> out(32 * nonces.size());
+        check(bm_header_hash_gpu(ctx_, header, nonces.data(), nonces.size(), out.data()), "bm_header_hash_gpu");
+        return out;
+    }
     // bitcoin.Hash for each nonce (hash.go:11-15), on the first device
     std::vector<uint64_t> hash(std::string_view msg, const std::vector<uint64_t>& nonces) {
         std::vector<uint64_t> out(nonces.size());
