@@ -1,0 +1,151 @@
+// bm_aux.hip -- the one unit of the host runtime with device code: the small
+// kernels of bm_aux_kernels.hpp, the host wrapper the searches launch the
+// second-pass reduction through, and the entry points outside the search
+// path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu).  See bm_runtime.hpp
+// for the layout of the host runtime.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "bm_aux_kernels.hpp"
+#include "bm_runtime.hpp"
+
+namespace bm {
+
+static_assert(kCtrClockSlot == kClockSlot, "the host reads the clock stamps where the kernels write them");
+
+int launch_reduce_partials(const Partial* part, uint32_t n, Partial* out, hipStream_t s) {
+    reduce_partials<<<1, kReduceThreads, 0, s>>>(part, n, out);
+    return hip_status(hipGetLastError());
+}
+
+namespace {
+
+// bm_reduce_gpu: n partials, one per lane, through block_min (ds_swizzle
+// butterflies, readlane, LDS) and then reduce_partials -- the reductions the
+// search uses above its per-lane scans.
+int reduce_impl(bm_ctx* ctx, const bm_result_t* in, size_t n, bm_result_t* out) {
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    const size_t blocks = (n + kBlock - 1) / kBlock;
+    BM_TRY(grow(d, d.d_test, d.test_cap, n + blocks + 1));
+    Partial* d_in = d.d_test;
+    Partial* d_blk = d.d_test + n;
+    Partial* d_out = d_blk + blocks;
+    if (n) BM_HIP(hipMemcpyAsync(d_in, in, n * sizeof(Partial), hipMemcpyHostToDevice, d.stream));
+    if (blocks) {
+        lane_partials_min<<<dim3((uint32_t)blocks), kBlock, 0, d.stream>>>(d_in, (uint32_t)n, d_blk);
+        BM_HIP(hipGetLastError());
+    }
+    BM_TRY(launch_reduce_partials(d_blk, (uint32_t)blocks, d_out, d.stream));
+    Partial r;
+    BM_HIP(hipMemcpyAsync(&r, d_out, sizeof r, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    out->hash = r.hash;
+    out->nonce = r.nonce;
+    return BM_OK;
+}
+
+int hash_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n, uint64_t* out) {
+    if (n == 0) return BM_OK;
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    HashArgs A;
+    std::memset(&A, 0, sizeof A);
+    // midstate over the whole 64-byte blocks of "msg "
+    const uint64_t pre = (uint64_t)len + 1;
+    const uint64_t full = pre / 64;
+    uint32_t st[8];
+    for (int i = 0; i < 8; ++i) st[i] = kIV256[i];
+    uint8_t blk[64];
+    for (uint64_t b = 0; b < full; ++b) {
+        for (int i = 0; i < 64; ++i) {
+            const uint64_t pos = b * 64 + (uint64_t)i;
+            blk[i] = pos < len ? msg[pos] : (uint8_t)' ';
+        }
+        host::compress_bytes(st, blk);
+    }
+    std::memcpy(A.mid, st, sizeof st);
+    A.tail_len = (uint32_t)(pre - full * 64);
+    for (uint32_t i = 0; i < A.tail_len; ++i) {
+        const uint64_t pos = full * 64 + i;
+        A.tail[i] = pos < len ? msg[pos] : (uint8_t)' ';
+    }
+    A.total_prefix = pre;
+    A.n = n;
+    BM_TRY(grow(d, d.d_hash_io, d.hash_cap, n, 2 * sizeof(uint64_t)));
+    BM_HIP(hipMemcpyAsync(d.d_hash_io, nonces, n * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream));
+    const uint64_t grid = (n + kHashThreads - 1) / kHashThreads;
+    hash_kernel<<<dim3((uint32_t)grid), kHashThreads, 0, d.stream>>>(A, d.d_hash_io, d.d_hash_io + n);
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipMemcpyAsync(out, d.d_hash_io + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    return BM_OK;
+}
+
+// bm_header_hash_gpu: the full double hash of arbitrary nonces on the first
+// device, most significant byte first.
+int header_hash_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* nonces, size_t n, uint8_t* out) {
+    if (n == 0) return BM_OK;
+    if (!g_header_hash) return BM_EINTERNAL;
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    HeaderHashArgs A;
+    std::memset(&A, 0, sizeof A);
+    uint32_t st[8];
+    for (int i = 0; i < 8; ++i) st[i] = kIV256[i];
+    host::compress_bytes(st, header);
+    std::memcpy(A.mid, st, sizeof st);
+    for (int i = 0; i < 3; ++i) A.w[i] = host::load_be32(header + 64 + 4 * i);
+    A.n = (uint32_t)n;
+    BM_TRY(grow(d, d.d_hdr_io, d.hdr_cap, n, 9 * sizeof(uint32_t)));
+    std::vector<uint32_t> words(8 * n);
+    uint32_t* d_in = d.d_hdr_io;
+    uint32_t* d_out = d.d_hdr_io + n;
+    BM_HIP(hipMemcpyAsync(d_in, nonces, n * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    const uint32_t grid = (uint32_t)((n + 63) / 64);
+    void* args[] = {&A, &d_in, &d_out};
+    BM_HIP(hipLaunchKernel(g_header_hash, dim3(grid), dim3(64), args, 0, d.stream));
+    BM_HIP(hipMemcpyAsync(words.data(), d_out, 8 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    // digest word k (big-endian) holds digest bytes 4k..4k+3; the hash is the
+    // digest reversed
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t w = words[8 * i + k];
+            uint8_t* o = out + 32 * i + 4 * (7 - k);
+            o[0] = (uint8_t)w;
+            o[1] = (uint8_t)(w >> 8);
+            o[2] = (uint8_t)(w >> 16);
+            o[3] = (uint8_t)(w >> 24);
+        }
+    return BM_OK;
+}
+
+}  // namespace
+}  // namespace bm
+
+extern "C" {
+
+int bm_reduce_gpu(bm_ctx_t* ctx, const bm_result_t* parts, size_t n, bm_result_t* out) {
+    if (!ctx || !out || (n && !parts) || n > BM_MAX_REDUCE) return BM_EINVAL;
+    bm::DeviceGuard guard;
+    bm_result_t r;
+    int rc = bm::reduce_impl(ctx, parts, n, &r);
+    if (rc == BM_OK) *out = r;
+    return rc;
+}
+
+int bm_hash_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n, uint64_t* out) {
+    if (!ctx || (n && (!nonces || !out)) || (len && !msg) || len > BM_MAX_MSG_LEN) return BM_EINVAL;
+    bm::DeviceGuard guard;
+    return bm::hash_impl(ctx, msg, len, nonces, n, out);
+}
+
+int bm_header_hash_gpu(bm_ctx_t* ctx, const uint8_t* header, const uint32_t* nonces, size_t n, uint8_t* out) {
+    if (!ctx || !header || (n && (!nonces || !out)) || n > BM_MAX_HEADER_HASHES) return BM_EINVAL;
+    bm::DeviceGuard guard;
+    return bm::guarded([&] { return bm::header_hash_impl(ctx, header, nonces, n, out); });
+}
+
+}  // extern "C"

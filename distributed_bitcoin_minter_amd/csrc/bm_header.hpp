@@ -1,5 +1,5 @@
 // bm_header.hpp -- Bitcoin block-header search: what the host works out once
-// per call, shared by the launcher (bm_api.hip), the kernels
+// per call, shared by the launcher (bm_search.cpp), the kernels
 // (bm_header_kernels.hpp) and a stand-alone CPU check (tools/header_precompute_check.cpp).
 // Plain C++: no HIP in here.
 //

@@ -1,6 +1,6 @@
 // bm_header_inst.hip -- the block-header kernels' build unit: header_kernel
 // and header_hash_kernel (bm_header_kernels.hpp), registered with the launcher
-// (bm_api.hip) at load time, the way bm_inst.hip registers the search kernels.
+// (bm_search.cpp) at load time, the way bm_inst.hip registers the search kernels.
 #include "bm_header_kernels.hpp"
 
 extern "C" void bm_register_header_kernels(const void* search_fn, const void* hash_fn);

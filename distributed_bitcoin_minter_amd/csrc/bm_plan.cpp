@@ -196,4 +196,14 @@ std::vector<Piece> slot_pieces(uint64_t lower, uint64_t upper, int n, const std:
     return out;
 }
 
+LaunchGeometry launch_geometry(uint64_t tasks, uint64_t task_nonces, uint64_t lane_chunk, uint64_t resident,
+                               uint32_t block) {
+    const uint64_t m_max = std::max<uint64_t>(1, lane_chunk / task_nonces);
+    const uint64_t m = std::max<uint64_t>(1, std::min<uint64_t>(m_max, tasks / (8 * resident * (uint64_t)block)));
+    const uint64_t chunks = (tasks + 64 * m - 1) / (64 * m);
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((chunks + 3) / 4, resident));
+    const uint64_t k = (chunks + grid * 4 - 1) / (grid * 4);  // chunks per wave (approx.)
+    return LaunchGeometry{(uint32_t)m, chunks, (uint32_t)grid, k * m};
+}
+
 }  // namespace bm

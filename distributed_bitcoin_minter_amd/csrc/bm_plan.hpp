@@ -46,4 +46,21 @@ std::vector<Piece> split_range(uint64_t lower, uint64_t upper, int n);
 // process group derives the same pieces.  An empty piece has lo > hi.
 std::vector<Piece> slot_pieces(uint64_t lower, uint64_t upper, int n, const std::vector<uint32_t>& shares);
 
+// The grid of one persistent launch that drains `tasks` tasks (tasks >= 1) of
+// task_nonces nonces each through a work counter.  A wave dequeues a chunk of
+// 64 * chunk_m tasks at a time: chunk_m is about lane_chunk nonces per lane,
+// but small enough for ~8 dequeues per resident lane, so the launch drains
+// evenly (small launches: 1).  The grid is at most one resident set of
+// workgroups (`resident` of them, `block` threads = block / 64 waves each;
+// the sizing assumes 4 waves); a surplus workgroup would only find the
+// counter exhausted.  Pure arithmetic, exact for tasks up to 2^63.
+struct LaunchGeometry {
+    uint32_t chunk_m;           // tasks per lane per dequeued chunk
+    uint64_t chunks;            // ceil(tasks / (64 * chunk_m))
+    uint32_t grid;              // workgroups
+    uint64_t tasks_per_thread;  // tasks per lane when the chunks spread evenly (approx.)
+};
+LaunchGeometry launch_geometry(uint64_t tasks, uint64_t task_nonces, uint64_t lane_chunk, uint64_t resident,
+                               uint32_t block);
+
 }  // namespace bm

@@ -6,7 +6,7 @@ all_gather of the 16-byte partial {hash, nonce} per rank, followed by a
 lexicographic (hash, nonce) min, which equals the reference's sequential
 strict-'<' scan (miner.go:59-65).  Inside one process the
 same split is done by a multi-device bm_ctx with an RCCL allgather
-(csrc/bm_api.hip).  With torch.distributed's "nccl" backend (RCCL on ROCm)
+(csrc/bm_combine.cpp).  With torch.distributed's "nccl" backend (RCCL on ROCm)
 the gather runs over xGMI.  bench.py's torchrun ranks use the library's own
 RCCL group instead (bm_ctx_create_rank, rendezvous.py), with no torch.
 """
@@ -32,7 +32,7 @@ def split_range(lower: int, upper: int, n: int):
     return out
 
 
-SHARE_SCALE = 65536  # the fastest slot's share (bm_api.hip kShareScale)
+SHARE_SCALE = 65536  # the fastest slot's share (bm_search.cpp kShareScale)
 
 
 def slot_pieces(lower: int, upper: int, n: int, shares=None):

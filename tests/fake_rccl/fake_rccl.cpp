@@ -1,5 +1,5 @@
 // fake_rccl.cpp -- TEST INFRASTRUCTURE ONLY: a stand-in for the RCCL calls
-// libbtcminer.so makes (csrc/bm_api.hip), so that two or more rank processes
+// libbtcminer.so makes (csrc/bm_combine.cpp, bm_ctx.cpp), so that two or more rank processes
 // on ONE GPU can form a group.  Real RCCL refuses two ranks on one GPU, and
 // every box of this pool has one GPU, so without this the library's world > 1
 // group paths (the status-carrying allgather, BM_EPEER between live ranks,

@@ -11,6 +11,12 @@
 // and that replaying a segment the way search_kernel does (template words +
 // digits of v, compressed from the midstate, + the padding block) gives
 // SHA-256("msg nonce") computed directly (hash.go:13 message).
+//
+// Then, for random (tasks up to 2^63, nonces per task, lane chunk, resident
+// workgroups), the invariants of launch_geometry: the chunks cover the tasks
+// exactly, the grid is between 1 and what is resident or needed, and the
+// lanes' shares cover the tasks, all without overflow.
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <random>
@@ -51,6 +57,19 @@ uint64_t replay(const bm_segment_t& s, uint64_t v) {
     for (int b = 0; b < s.nbv; ++b) bm::host::compress(st, w + 16 * b);
     if (s.pad_block) bm::host::compress(st, s.pad_w);
     return ((uint64_t)st[0] << 32) | st[1];
+}
+
+// 0, or what launch_geometry(T, S, lane_chunk, resident, 256) got wrong
+const char* geometry_error(uint64_t T, uint64_t S, uint64_t lane_chunk, uint64_t resident) {
+    typedef unsigned __int128 u128;
+    const bm::LaunchGeometry g = bm::launch_geometry(T, S, lane_chunk, resident, 256);
+    if (g.chunk_m < 1 || g.chunk_m > std::max<uint64_t>(1, lane_chunk / S)) return "chunk_m";
+    if (g.chunks < 1) return "chunks";
+    const u128 per_chunk = (u128)64 * g.chunk_m;
+    if (!(per_chunk * g.chunks >= T && T > per_chunk * (g.chunks - 1))) return "chunks do not tile the tasks";
+    if (g.grid < 1 || g.grid > resident || g.grid > (g.chunks + 3) / 4) return "grid";
+    if ((u128)g.tasks_per_thread * g.grid * 4 * 64 < T) return "tasks_per_thread";
+    return nullptr;
 }
 
 int fail(const char* what, size_t L, uint64_t lo, uint64_t hi) {
@@ -104,6 +123,19 @@ int main(int argc, char** argv) {
         }
         if (segs.empty() || segs.back().nonce_base + segs.back().vhi != hi) return fail("end", L, lo, hi);
     }
-    std::printf("ok %d plans, %zu segments\n", iters, nseg_total);
+    const uint64_t kTaskNonces[3] = {10, 100, 256};  // the decimal search's two task sizes, the header search's
+    for (int it = 0; it < 20 * iters; ++it) {
+        uint64_t T = it % 16 == 0 ? 1ull << 63 : (rng() >> (rng() % 64)) % (1ull << 63) + 1;
+        if (it % 16 == 1) T = rng() % 100000 + 1;
+        const uint64_t S = kTaskNonces[rng() % 3];
+        const uint64_t lane_chunk = 10 + rng() % 99991;  // BTCMINER_CHUNK's range
+        const uint64_t resident = 1 + rng() % (it % 3 == 0 ? 8 : 32 * 1024);  // up to 32 blocks on each of 1024 CUs
+        if (const char* what = geometry_error(T, S, lane_chunk, resident)) {
+            std::printf("FAIL geometry %s T=%llu S=%llu chunk=%llu resident=%llu\n", what, (unsigned long long)T,
+                        (unsigned long long)S, (unsigned long long)lane_chunk, (unsigned long long)resident);
+            return 1;
+        }
+    }
+    std::printf("ok %d plans, %zu segments, %d geometries\n", iters, nseg_total, 20 * iters);
     return 0;
 }
