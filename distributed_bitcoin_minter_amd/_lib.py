@@ -87,6 +87,16 @@ HEADER_BYTES = 80
 U32_MAX = (1 << 32) - 1
 U256_MAX = (1 << 256) - 1
 BM_MAX_HEADER_HASHES = 1 << 24
+BM_MAX_HEADER_HITS = 1 << 20
+
+
+class HeaderHit(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("nonce", c_u32), ("reserved", c_u32)]
+
+
+class HeaderHitsResult(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("nonce", c_u32), ("reserved", c_u32), ("count", c_u64),
+                ("stored", c_u64)]
 
 
 class Segment(ctypes.Structure):
@@ -164,6 +174,8 @@ def _open(path):
         "bm_search_hits_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, c_u64, c_u64, c_u64, P(Result),
                                 ctypes.c_size_t, P(HitsResult)], ctypes.c_int),
         "bm_search_header_gpu": ([vp, ctypes.c_char_p, c_u32, c_u32, ctypes.c_char_p, P(HeaderResult)], ctypes.c_int),
+        "bm_search_header_hits_gpu": ([vp, ctypes.c_char_p, c_u32, c_u32, ctypes.c_char_p, P(HeaderHit),
+                                       ctypes.c_size_t, P(HeaderHitsResult)], ctypes.c_int),
         "bm_header_hash_gpu": ([vp, ctypes.c_char_p, P(c_u32), ctypes.c_size_t, P(ctypes.c_uint8)], ctypes.c_int),
         "bm_header_target_from_bits": ([c_u32, P(ctypes.c_uint8)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
@@ -435,6 +447,32 @@ class Context:
         check(self._lib.bm_search_header_gpu(self.handle, header, nonce_lo, nonce_hi, tgt, ctypes.byref(r)),
               "bm_search_header_gpu")
         return bool(r.found), int.from_bytes(bytes(r.hash), "big"), r.nonce
+
+    def search_header_hits(self, header: bytes, nonce_lo: int = 0, nonce_hi: int = U32_MAX, target=U256_MAX,
+                           cap: int = 4096):
+        """Bitcoin block header: every nonce of [nonce_lo, nonce_hi] whose
+        double SHA-256 is <= target -> (count, hits, (best hash, best nonce)):
+        hits is the list of (hash, nonce) in ascending nonce order, or None
+        when count > cap (nothing is returned then; count is still exact);
+        the best share is search_header()'s answer at target 0.  cap = 0 only
+        counts.  An empty range gives (0, [], (2^256-1, 2^32-1))."""
+        header = _header_bytes(header)
+        for v, what in ((nonce_lo, "nonce_lo"), (nonce_hi, "nonce_hi")):
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U32_MAX:
+                raise ValueError(f"{what} must be in 0..2^32-1, got {v!r}")
+        tgt = _target_bytes(target)
+        if not isinstance(cap, int) or isinstance(cap, bool) or not 0 <= cap <= BM_MAX_HEADER_HITS:
+            raise ValueError(f"cap must be in 0..{BM_MAX_HEADER_HITS}, got {cap!r}")
+        r = HeaderHitsResult()
+        buf = (HeaderHit * cap)() if cap > 0 else None
+        check(self._lib.bm_search_header_hits_gpu(self.handle, header, nonce_lo, nonce_hi, tgt, buf, cap,
+                                                  ctypes.byref(r)), "bm_search_header_hits_gpu")
+        hits = None
+        if r.count <= cap:
+            raw = bytes(buf)[:ctypes.sizeof(HeaderHit) * r.stored] if buf is not None else b""
+            hits = [(int.from_bytes(raw[o:o + 32], "big"), int.from_bytes(raw[o + 32:o + 36], "little"))
+                    for o in range(0, len(raw), ctypes.sizeof(HeaderHit))]
+        return r.count, hits, (int.from_bytes(bytes(r.hash), "big"), r.nonce)
 
     def header_hash_many(self, header: bytes, nonces):
         """The header's double SHA-256 under each nonce, as integers (the

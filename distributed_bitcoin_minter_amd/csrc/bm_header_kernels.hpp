@@ -1,6 +1,9 @@
 // bm_header_kernels.hpp -- gfx950 kernels for the Bitcoin block-header search
-// (bm_search_header_gpu / bm_header_hash_gpu), built from the SHA-256 pieces
-// of bm_kernels.hpp.  A build unit of its own (bm_header_inst.hip).
+// (bm_search_header_gpu / bm_search_header_hits_gpu / bm_header_hash_gpu),
+// built from the SHA-256 pieces of bm_kernels.hpp.  Two build units:
+// bm_header_inst.hip (header_kernel, header_hash_kernel) and
+// bm_header_hits_inst.hip (header_hits_kernel: header_kernel's body in hits
+// mode; the two share bm_header_body.inc).
 //
 // header_kernel, per nonce n (bm_header.hpp has the per-call host part):
 //   * W3 = bswap32(n).  n = (task << 8) | j: the task part is per lane, the
@@ -137,82 +140,27 @@ BM_DEV bool le256(const uint32_t (&h)[8], const uint32_t (&t)[8]) {
 // Work distribution as search_body's: each wave dequeues chunks of
 // 64 * chunk_m consecutive tasks from the launch's counter (one returning
 // atomic per chunk, lane 0), lane l taking tasks base + l, base + 64 + l, ...
+// The body is bm_header_body.inc, shared with header_hits_kernel.
+#ifdef BM_HEADER_HITS_UNIT
+// header_kernel in hits mode (bm_search_header_hits_gpu), the one kernel of
+// its build unit (bm_header_hits_inst.hip defines BM_HEADER_HITS_UNIT), so the
+// unit of the two kernels below holds what it always held.  Occupancy request
+// as for header_kernel.  hit_buf holds hit_cap entries of 16 bytes, 16-byte
+// aligned.
+__global__ __launch_bounds__(kBlock) BM_HEADER_KATTR void header_hits_kernel(
+    const HeaderArgs A, Partial* __restrict__ part, unsigned long long* __restrict__ counter,
+    unsigned long long* __restrict__ hit_count, Partial* __restrict__ hit_buf, const uint64_t hit_cap) {
+#define BM_HEADER_HITS 1
+#include "bm_header_body.inc"
+#undef BM_HEADER_HITS
+}
+#else
 __global__ __launch_bounds__(kBlock) BM_HEADER_KATTR void header_kernel(
     const HeaderArgs A, Partial* __restrict__ part, unsigned long long* __restrict__ counter,
     unsigned long long* __restrict__ hit) {
-    uint64_t best_h = ~0ull, best_n = ~0ull;
-    const uint32_t thi = A.tgt[0];
-    uint32_t bh = 0xFFFFFFFFu;  // max(top word of best_h, thi)
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t ntask = A.ntask;
-    const uint32_t chunk = 64u * A.chunk_m;
-
-    for (;;) {
-        uint64_t base = 0, seen = 0;
-        if (lane == 0) {
-            base = atomicAdd(counter, (unsigned long long)chunk);
-            seen = __hip_atomic_load(hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        base = readfirstlane_u64(base);
-        if (base >= ntask) break;
-        seen = readfirstlane_u64(seen);
-        // the chunk's lowest nonce, in 64 bits (tasks stay below 2^24)
-        if (seen < ((uint64_t)(A.t0 + (uint32_t)base) << kHeaderTaskBits)) break;
-        for (uint32_t i = 0; i < A.chunk_m; ++i) {
-            const uint64_t tt = base + 64u * i + lane;
-            if (tt >= ntask) break;
-            const uint32_t nb = (A.t0 + (uint32_t)tt) << kHeaderTaskBits;  // the task's first nonce
-            const uint32_t wl = __builtin_bswap32(nb);                     // its part of W3
-            const uint32_t s0wl = ssig0(wl);
-
-            uint32_t J = 0;  // the inner counter's part of W3: j << 24
-            for (uint32_t j = 0; j < kHeaderTaskNonces; ++j, J += 1u << 24) {
-                const uint32_t x = wl | J;
-                const uint32_t s0x = s0wl ^ ssig0_salu(J);
-
-                // ---- first hash: block 2 from round 3 on ----
-                uint32_t s[8];  // entering round 4: role r in s[(r - 4) & 7]
-                s[4] = A.a3k + x;  // a
-                s[5] = A.r4[0];    // b
-                s[6] = A.r4[1];    // c
-                s[7] = A.r4[2];    // d
-                s[0] = A.e3k + x;  // e
-                s[1] = A.r4[3];    // f
-                s[2] = A.r4[4];    // g
-                s[3] = A.r4[5];    // h
-                header_block2(A, x, s0x, s);
-
-                // ---- second hash: the digest, one block from the IV ----
-                uint32_t w[16];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) w[q] = A.mid[q] + s[q];
-                uint32_t z[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) z[q] = kIV256[q];
-                static_for<0, 61>([&](auto I) { block_round<DigestBlock, decltype(I)::value>(z, w); });
-                // entering round 61, role e (the final h) lives in z[(4 - 61) & 7]
-                const uint32_t h0 = __builtin_bswap32(kIV256[7] + z[(4 - 61) & 7]);
-
-                if (__builtin_expect(h0 <= bh, 0)) {
-                    static_for<61, 64>([&](auto I) { block_round<DigestBlock, decltype(I)::value>(z, w); });
-                    uint32_t hw[8];  // the hash, most significant word first
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) hw[q] = __builtin_bswap32(kIV256[7 - q] + z[7 - q]);
-                    const uint32_t n = nb + j;
-                    if (n >= A.lo && n <= A.hi) {
-                        if (le256(hw, A.tgt)) atomicMin(hit, (unsigned long long)n);
-                        const uint64_t top = ((uint64_t)hw[0] << 32) | hw[1];
-                        if (lex_less(top, n, best_h, best_n)) {
-                            best_h = top;
-                            best_n = n;
-                            bh = hw[0] > thi ? hw[0] : thi;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (block_min<kBlock>(best_h, best_n)) part[A.part_off + blockIdx.x] = Partial{best_h, best_n};
+#define BM_HEADER_HITS 0
+#include "bm_header_body.inc"
+#undef BM_HEADER_HITS
 }
 
 // One lane per nonce: the full double hash by the plain compression, from
@@ -251,5 +199,7 @@ __global__ __launch_bounds__(kHeaderHashThreads) void header_hash_kernel(const H
 #pragma unroll
     for (int k = 0; k < 8; ++k) out[8ull * i + k] = st[k];
 }
+
+#endif  // BM_HEADER_HITS_UNIT
 
 }  // namespace bm

@@ -2,7 +2,7 @@
 // public interface is include/btcminer.h):
 //   bm_ctx.cpp     contexts and devices: lifetime, buffers, knobs, the rank join
 //   bm_combine.cpp the combine of a search's partials (RCCL allgather or host copies)
-//   bm_search.cpp  the four searches: kernel tables, sizing, enqueue, statistics
+//   bm_search.cpp  the five searches: kernel tables, sizing, enqueue, statistics
 //   bm_aux.hip     the only unit with device code: the kernels of bm_aux_kernels.hpp,
 //                  a host wrapper that launches the reduction, and the entry points
 //                  built on them (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu)
@@ -78,7 +78,7 @@ struct DeviceCtx {
     unsigned long long* d_hit = nullptr;  // target search: the lowest nonce at or below the target seen so
                                           // far (all-ones: none); an allocation, hence a line, of its own
     unsigned long long* h_hit = nullptr;  // pinned copy
-    unsigned long long* d_hcount = nullptr;  // hit enumeration: the hits counted so far (an allocation of its own)
+    unsigned long long* d_hcount = nullptr;  // hit enumerations: the hits counted so far (an allocation of its own)
     unsigned long long* h_hcount = nullptr;  // pinned copy
     Partial* d_hbuf = nullptr;               // the first hbuf_cap of them, in the order the lanes took their slots
     size_t hbuf_cap = 0;                     // grows to the largest cap asked for
@@ -106,17 +106,21 @@ struct DeviceCtx {
     double wall_clock_hz = 100e6;                  // s_memrealtime rate
 };
 
-// The four searches share one plan -> enqueue -> combine -> stats path
+// The five searches share one plan -> enqueue -> combine -> stats path
 // (bm_search.cpp); a Mode says which one a call is, and carries what its
 // kernels take beyond a launch's own arguments.  DESIGN.md section 1, "Host
 // runtime layout", lists what a mode changes.
-enum class Kind { Search, Target, Hits, Header };
+enum class Kind { Search, Target, Hits, Header, HeaderHits };
 struct Mode {
     Kind kind = Kind::Search;
-    uint64_t target = 0;  // Target, Hits: the 64-bit bound (Header: its 256-bit target is in HeaderArgs)
-    uint64_t cap = 0;     // Hits: entries of the hit buffer
+    uint64_t target = 0;  // Target, Hits: the 64-bit bound (Header, HeaderHits: their 256-bit target is in HeaderArgs)
+    uint64_t cap = 0;     // Hits, HeaderHits: entries of the hit buffer
     // first hit wins: launches in ascending nonce order, one hit word per device
     bool first_hit() const { return kind == Kind::Target || kind == Kind::Header; }
+    // every hit: a counter and a buffer of 16-byte entries per device (d_hcount, d_hbuf)
+    bool every_hit() const { return kind == Kind::Hits || kind == Kind::HeaderHits; }
+    // a block-header call: one launch of HeaderArgs per device
+    bool header() const { return kind == Kind::Header || kind == Kind::HeaderHits; }
 };
 
 // One kernel launch of a call, with what the ordering and the accounting of
@@ -125,7 +129,7 @@ struct Launch {
     const void* fn;
     union {
         SearchArgs search;  // Search, Target, Hits
-        HeaderArgs header;  // Header
+        HeaderArgs header;  // Header, HeaderHits
     } args;                 // the kernel's first parameter, by value
     uint64_t first_nonce;  // the lowest nonce it scans
     uint64_t tasks;        // what its work counter runs up to

@@ -1,6 +1,6 @@
-// bm_search.cpp -- the four searches of include/btcminer.h (bm_search_gpu,
-// bm_search_target_gpu, bm_search_hits_gpu, bm_search_header_gpu) over one
-// path: plan and size every launch, enqueue each device's launches and its
+// bm_search.cpp -- the five searches of include/btcminer.h (bm_search_gpu,
+// bm_search_target_gpu, bm_search_hits_gpu, bm_search_header_gpu,
+// bm_search_header_hits_gpu) over one path: plan and size every launch, enqueue each device's launches and its
 // second-pass reduction, combine the devices' partials, record the stats.
 // What differs between them is a Mode (bm_runtime.hpp) and the code around
 // that path in each *_impl.  Plain C++ over the HIP host API.
@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "bm_header_hits.hpp"
 #include "bm_runtime.hpp"
 
 namespace bm {
@@ -33,6 +34,8 @@ const void* g_target[2][64];
 const void* g_hits[2][64];
 // header_kernel, filled (with g_header_hash) by bm_header_inst.hip at load time
 const void* g_header_search = nullptr;
+// header_hits_kernel, filled by bm_header_hits_inst.hip at load time
+const void* g_header_hits = nullptr;
 
 // Balance (bm_ctx_set_balance): a device's rate is measured only when its
 // piece held at least this many nonces (about 20 ms of one MI355X), and the
@@ -63,6 +66,8 @@ extern "C" void bm_register_header_kernels(const void* search_fn, const void* ha
     bm::g_header_search = search_fn;
     bm::g_header_hash = hash_fn;
 }
+
+extern "C" void bm_register_header_hits_kernel(const void* fn) { bm::g_header_hits = fn; }
 
 namespace bm {
 namespace {
@@ -170,10 +175,12 @@ int size_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const bm_segment_t& s, uin
     return BM_OK;
 }
 
-// One device's launch of header_kernel: its piece [lo, hi] of the nonce range
-// in tasks of 256 nonces.
-int size_header_launch(bm_ctx* ctx, DeviceCtx& d, const HeaderArgs& base, uint32_t lo, uint32_t hi, Launch& L) {
-    if (!g_header_search) return BM_EINTERNAL;
+// One device's launch of header_kernel (Header) or header_hits_kernel
+// (HeaderHits): its piece [lo, hi] of the nonce range in tasks of 256 nonces.
+int size_header_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const HeaderArgs& base, uint32_t lo, uint32_t hi,
+                       Launch& L) {
+    const void* fn = kind == Kind::HeaderHits ? g_header_hits : g_header_search;
+    if (!fn) return BM_EINTERNAL;
     std::memset(&L, 0, sizeof L);
     HeaderArgs& A = L.args.header;
     A = base;
@@ -182,10 +189,10 @@ int size_header_launch(bm_ctx* ctx, DeviceCtx& d, const HeaderArgs& base, uint32
     A.t0 = lo >> kHeaderTaskBits;
     A.ntask = (hi >> kHeaderTaskBits) - A.t0 + 1;
     const LaunchGeometry g = launch_geometry(A.ntask, kHeaderTaskNonces, ctx->lane_chunk,
-                                             resident_blocks(ctx, d, g_header_search), kBlock);
+                                             resident_blocks(ctx, d, fn), kBlock);
     A.chunk_m = g.chunk_m;
     A.part_off = 0;
-    L.fn = g_header_search;
+    L.fn = fn;
     L.first_nonce = lo;
     L.tasks = A.ntask;
     L.task_nonces = kHeaderTaskNonces;
@@ -223,13 +230,13 @@ int ensure_buffers(DeviceCtx& d, const Mode& mode, const std::vector<Launch>& la
     for (const Launch& L : launches) parts += L.stat.grid;
     BM_TRY(grow(d, d.d_part, d.part_cap, std::max(parts, kMinPartials)));
     BM_TRY(ensure_counters(d, launches.size()));
-    if (mode.kind != Kind::Hits) return BM_OK;
+    if (!mode.every_hit()) return BM_OK;
     return grow(d, d.d_hbuf, d.hbuf_cap, std::max<size_t>(mode.cap, 1), sizeof(Partial), false, BM_ENOMEM);
 }
 
 // Stage 1 of a search: plan and size every launch of every device.  A decimal
 // search (msg, len): one launch per segment of the device's piece.  A header
-// search (base): one launch per device.
+// search or enumeration (base): one launch per device.
 int plan_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* msg, size_t len, const HeaderArgs* base,
                   uint64_t lower, uint64_t upper, std::vector<std::vector<Launch>>& launches) {
     const std::vector<Piece> pieces = plan_pieces(ctx, lower, upper);
@@ -258,7 +265,8 @@ int plan_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* msg, size_t len,
         uint32_t off = 0;
         for (size_t i = 0; i < (base ? 1 : segs.size()); ++i) {
             Launch L;
-            BM_TRY(base ? size_header_launch(ctx, d, *base, (uint32_t)pieces[di].lo, (uint32_t)pieces[di].hi, L)
+            BM_TRY(base ? size_header_launch(ctx, d, mode.kind, *base, (uint32_t)pieces[di].lo,
+                                             (uint32_t)pieces[di].hi, L)
                         : size_launch(ctx, d, mode.kind, segs[i], off, L));
             L.stat.device = (int)di;
             off += L.stat.grid;
@@ -300,7 +308,7 @@ int enqueue_device(bm_ctx* ctx, int di, const Mode& mode, std::vector<Launch>& l
         *d.h_hit = ~0ull;
         BM_HIP(hipMemsetAsync(d.d_hit, 0xFF, sizeof(unsigned long long), d.stream));
     }
-    if (mode.kind == Kind::Hits) {
+    if (mode.every_hit()) {
         *d.h_hcount = 0;
         BM_HIP(hipMemsetAsync(d.d_hcount, 0, sizeof(unsigned long long), d.stream));
     }
@@ -338,6 +346,7 @@ int enqueue_device(bm_ctx* ctx, int di, const Mode& mode, std::vector<Launch>& l
             case Kind::Target: more({&target, &d.d_hit}); break;
             case Kind::Hits: more({&target, &d.d_hcount, &d.d_hbuf, &cap}); break;
             case Kind::Header: more({&d.d_hit}); break;
+            case Kind::HeaderHits: more({&d.d_hcount, &d.d_hbuf, &cap}); break;
         }
         BM_HIP(hipLaunchKernel(L.fn, dim3(L.stat.grid), dim3(kBlock), params, 0, s));
         if (timed) BM_HIP(hipEventRecord(d.ev[2 * li + 1], s));
@@ -352,7 +361,7 @@ int enqueue_device(bm_ctx* ctx, int di, const Mode& mode, std::vector<Launch>& l
     if (mark) BM_HIP(hipEventRecord(d.bal[1], d.stream));
     if (mode.first_hit())
         BM_HIP(hipMemcpyAsync(d.h_hit, d.d_hit, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
-    if (mode.kind == Kind::Hits)
+    if (mode.every_hit())
         BM_HIP(hipMemcpyAsync(d.h_hcount, d.d_hcount, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
     // the strips: clock stamps, for the launch stats; first hit wins: the dequeue counters
     if (((BM_CLOCK_PROBE && ctx->timing) || mode.first_hit()) && !launches.empty())
@@ -737,6 +746,91 @@ int header_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, co
     return BM_OK;
 }
 
+// bm_search_header_hits_gpu: a full scan, one launch of header_hits_kernel per
+// device over the partitioner's pieces.  Each device appends {top 64 bits, nonce}
+// to d_hbuf through d_hcount (what bm_search_hits_gpu uses, with the same
+// 16-byte entries); the host reads every counter back and, only when their sum
+// fits in cap, the entries, which header_hits_collect sorts, rehashes in full
+// and checks.  The best share is header_impl's found = 0 answer.  hits and out
+// are written last, on success only.
+int header_hits_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, const uint8_t* target,
+                     bm_header_hit_t* hits, size_t cap, bm_header_hits_result_t* out) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const Mode mode{Kind::HeaderHits, 0, (uint64_t)cap};
+    begin_call(ctx, mode);
+    const int ndev = (int)ctx->devs.size();
+    bm_header_hits_result_t r;
+    std::memset(&r, 0, sizeof r);
+    if (lo > hi) {
+        std::memset(r.hash, 0xFF, sizeof r.hash);
+        r.nonce = 0xFFFFFFFFu;
+        *out = r;
+        return BM_OK;
+    }
+
+    HeaderArgs base;
+    std::memset(&base, 0, sizeof base);
+    host::header_precompute(header, base);
+    for (int i = 0; i < 8; ++i) base.tgt[i] = host::load_be32(target + 4 * i);
+
+    std::vector<std::vector<Launch>> launches(ndev);
+    std::vector<uint32_t> first(ndev, 0);
+    std::vector<Partial> got;
+    std::vector<bm_header_hit_t> list;
+    Partial best{UINT64_MAX, UINT64_MAX};
+    int rc = guarded([&] { return plan_launches(ctx, mode, nullptr, 0, &base, lo, hi, launches); });
+    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
+    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
+    if (rc != BM_OK) return fail_call(ctx, rc);
+
+    uint64_t count = 0;
+    std::vector<size_t> counts(ndev, 0);
+    for (int di = 0; di < ndev; ++di) {
+        if (launches[di].empty()) continue;
+        const uint64_t c = *ctx->devs[di].h_hcount;
+        if (c > ctx->devs[di].piece_nonces) return fail_call(ctx, BM_EINTERNAL);  // a nonce counts once
+        counts[di] = (size_t)c;
+        count += c;
+    }
+    if (count <= cap && count > 0) {
+        rc = guarded([&] {
+            got.resize((size_t)count);
+            list.resize((size_t)count);
+            size_t at = 0;
+            for (int di = 0; di < ndev; ++di) {
+                DeviceCtx& d = ctx->devs[di];
+                if (counts[di] == 0) continue;
+                BM_HIP(hipSetDevice(d.id));
+                BM_HIP(hipMemcpyAsync(got.data() + at, d.d_hbuf, counts[di] * sizeof(Partial), hipMemcpyDeviceToHost,
+                                      d.stream));
+                BM_HIP(hipStreamSynchronize(d.stream));
+                at += counts[di];
+            }
+            return host::header_hits_collect(header, target, lo, hi, got.data(), counts.data(), ndev, list.data());
+        });
+        if (rc != BM_OK) return fail_call(ctx, rc);
+    }
+
+    // the best share: the device's claim against the host's hash of that nonce
+    if (best.nonce > 0xFFFFFFFFull) return fail_call(ctx, BM_EINTERNAL);  // a non-empty range always has a minimum
+    host::header_hash_msb(header, (uint32_t)best.nonce, r.hash);
+    r.nonce = (uint32_t)best.nonce;
+    uint64_t top = 0;
+    for (int i = 0; i < 8; ++i) top = (top << 8) | r.hash[i];
+    if (top != best.hash) return fail_call(ctx, BM_EINTERNAL);
+    // ... and against the count: a best share at or below the target is itself a hit
+    if (count == 0 && std::memcmp(r.hash, target, 32) <= 0) return fail_call(ctx, BM_EINTERNAL);
+
+    rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
+    if (rc != BM_OK) return fail_call(ctx, rc);
+
+    r.count = count;
+    r.stored = count <= cap ? count : 0;
+    if (r.stored) std::memcpy(hits, list.data(), (size_t)r.stored * sizeof(bm_header_hit_t));
+    *out = r;
+    return BM_OK;
+}
+
 }  // namespace
 }  // namespace bm
 
@@ -781,6 +875,20 @@ int bm_search_header_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t nonce_lo
     bm::DeviceGuard guard;
     bm_header_result_t r;
     int rc = bm::guarded([&] { return bm::header_impl(ctx, header, nonce_lo, nonce_hi, target, &r); });
+    if (rc == BM_OK) *out = r;
+    return rc;
+}
+
+int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t nonce_lo, uint32_t nonce_hi,
+                              const uint8_t* target, bm_header_hit_t* hits, size_t cap,
+                              bm_header_hits_result_t* out) {
+    if (!ctx || !header || !target || !out) return BM_EINVAL;
+    if (cap > BM_MAX_HEADER_HITS || (!hits && cap > 0)) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    bm::DeviceGuard guard;
+    bm_header_hits_result_t r;
+    int rc = bm::guarded(
+        [&] { return bm::header_hits_impl(ctx, header, nonce_lo, nonce_hi, target, hits, cap, &r); });
     if (rc == BM_OK) *out = r;
     return rc;
 }

@@ -269,9 +269,9 @@ int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t l
  * sign bit 0x00800000 is set or the value overflows 256 bits.
  *
  * Out of scope: rolling ntime or an extranonce past 2^32 nonces (the caller
- * changes the header and calls again; a call is a fraction of a second); hit
- * enumeration for headers; cancelling one device's work on another device's
- * hit; rank groups; the LSP server protocol. */
+ * changes the header and calls again; a call is a fraction of a second);
+ * cancelling one device's work on another device's hit; rank groups; the LSP
+ * server protocol. */
 #define BM_MAX_HEADER_HASHES (1u << 24)
 typedef struct bm_header_result {
     uint8_t hash[32]; /* found: H(nonce); else H of the best share's nonce */
@@ -284,6 +284,63 @@ int bm_search_header_gpu(bm_ctx_t* ctx, const uint8_t header[80], uint32_t nonce
 int bm_header_hash_gpu(bm_ctx_t* ctx, const uint8_t header[80], const uint32_t* nonces, size_t n,
                        uint8_t* out /* 32 * n */);
 int bm_header_target_from_bits(uint32_t nbits, uint8_t target[32]);
+
+/* ---- block-header shares: every nonce whose hash meets a target -----------
+ * bm_search_header_hits_gpu scans all of [nonce_lo, nonce_hi] (no early exit)
+ * and returns every n with H(n) <= target, plus the range's best share: what a
+ * pool miner submits for one header.  H, `hash` and `target` are as above: 256-bit
+ * numbers written MOST significant byte first, compared over the full 256 bits.
+ *   hits[0 .. stored) holds {H(n), n, 0} for every hit in ascending nonce order,
+ *     each nonce exactly once (every hash recomputed on the host).  count is
+ *     exact, always.
+ *   All or nothing: count > cap writes NOTHING to hits, stored = 0, and the
+ *     call still succeeds with the exact count; ask again with a larger buffer
+ *     or a smaller range.  No subset is ever returned.
+ *   hits == NULL with cap == 0 is a pure count.  cap > BM_MAX_HEADER_HITS, or
+ *     hits == NULL with cap > 0: BM_EINVAL.  A NULL ctx, header, target or out:
+ *     BM_EINVAL, before anything is dereferenced.
+ *   out->hash / out->nonce: the range's best share in full, exactly the answer
+ *     of bm_search_header_gpu with found = 0 (target 0): the minimum of
+ *     (H(n) >> 192, n).
+ *   nonce_lo > nonce_hi: hash all 0xFF, nonce = 0xFFFFFFFF, count = stored = 0,
+ *     hits untouched.  nonce_hi = 2^32-1 is legal.
+ * The result never depends on timing, residency, streams, BTCMINER_CHUNK,
+ * blocks per CU or the split.  On failure `out` and `hits` are untouched and
+ * the context stays usable (a device buffer that cannot grow to cap:
+ * BM_ENOMEM, and the context is as it was).
+ * Contexts: one device, or one process over several devices (a device listed
+ * N times included): the nonce range is cut by the partitioner, each device
+ * appends 16-byte entries {H(n) >> 192, n} to the buffer and counter that
+ * bm_search_hits_gpu uses, and the host sorts them by nonce, recomputes each
+ * full hash and checks the device's claim (BM_EINTERNAL if one fails) -- always
+ * by host copies.  A rank context with world > 1 returns BM_EINVAL.
+ * bm_ctx_set_balance does not learn from these calls; bm_ctx_set_test_fault
+ * applies as for a header search; bm_ctx_last_stats is filled, one launch per
+ * device (a launch of header_hits_kernel; nonces = the range size);
+ * bm_ctx_last_target_stats is not touched.
+ * Cost: that of a full bm_search_header_gpu scan while hits are rare.  Every
+ * hit is one atomic on one word per device and, when stored, one sha256d on
+ * the host.
+ *
+ * Out of scope: several headers in one call; extranonce or merkle rolling;
+ * cancelling across devices; rank groups; the LSP server protocol. */
+#define BM_MAX_HEADER_HITS (1u << 20) /* entries; each stored hit costs one host sha256d */
+typedef struct bm_header_hit {
+    uint8_t hash[32]; /* H(nonce) */
+    uint32_t nonce;
+    uint32_t reserved; /* 0 */
+} bm_header_hit_t;     /* 40 bytes */
+typedef struct bm_header_hits_result {
+    uint8_t hash[32];  /* the range's best share, in full: bm_search_header_gpu's found = 0 answer */
+    uint32_t nonce;    /* its nonce */
+    uint32_t reserved; /* 0 */
+    uint64_t count;    /* nonces of the range with H(n) <= target: exact, always */
+    uint64_t stored;   /* entries written to hits[]: count when count <= cap, else 0 */
+} bm_header_hits_result_t; /* 56 bytes */
+
+int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t header[80], uint32_t nonce_lo, uint32_t nonce_hi,
+                              const uint8_t target[32], bm_header_hit_t* hits, size_t cap,
+                              bm_header_hits_result_t* out);
 
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */

@@ -142,6 +142,21 @@ class Context {
         check(bm_search_header_gpu(ctx_, header, nonce_lo, nonce_hi, target, &r), "bm_search_header_gpu");
         return r;
     }
+    // every n in [nonce_lo, nonce_hi] whose double SHA-256 is <= target,
+    // ascending, into `hits` (resized to the result's `stored`: empty when
+    // count > cap), plus the exact count and the range's best share:
+    // bm_search_header_hits_gpu
+    bm_header_hits_result_t search_header_hits(const uint8_t header[80], uint32_t nonce_lo, uint32_t nonce_hi,
+                                               const uint8_t target[32], std::vector<bm_header_hit_t>& hits,
+                                               size_t cap) {
+        bm_header_hits_result_t r;
+        std::vector<bm_header_hit_t> buf(cap);
+        check(bm_search_header_hits_gpu(ctx_, header, nonce_lo, nonce_hi, target, cap ? buf.data() : nullptr, cap, &r),
+              "bm_search_header_hits_gpu");
+        buf.resize(static_cast<size_t>(r.stored));
+        hits = std::move(buf);
+        return r;
+    }
     // the double SHA-256 of the header under each nonce, 32 bytes each, most
     // significant byte first, on the first device: bm_header_hash_gpu
     std::vector<uint8_t> header_hash(const uint8_t header[80], const std::vector<uint32_t>& nonces) {

@@ -8,7 +8,9 @@ v_readlane (the generic padding-block kernel's) are counted and reported.
 --header: check header_kernel instead (the block-header search, the
 bm_header_inst unit), row "hdr", the same way; its per-nonce block is the loop
 block with the most VALU (its deepest loop is the rare path's wave scan for the
-64-bit atomicMin)."""
+64-bit atomicMin).
+--header-hits: check header_hits_kernel (the block-header share enumeration,
+the bm_header_hits_inst unit), row "hdrh", as --header does."""
 import glob
 import os
 import re
@@ -26,7 +28,8 @@ build = args[0] if args else os.path.join(ROOT, "distributed_bitcoin_minter_amd/
 bad = 0
 rows = []
 HEADER = "--header" in sys.argv
-for sfile in sorted(glob.glob(os.path.join(build, "*gfx950.s"))) if not HEADER else []:
+HEADER_HITS = "--header-hits" in sys.argv
+for sfile in sorted(glob.glob(os.path.join(build, "*gfx950.s"))) if not (HEADER or HEADER_HITS) else []:
     for name in isa_loops.kernels(sfile, "search_kernel"):
         m = re.search(r"search_kernel(_padc|_padk)?ILi(\d+)ELi(\d+)E(?:Li(\d+)E)?", name)
         if not m:
@@ -73,6 +76,14 @@ for sfile in sorted(glob.glob(os.path.join(build, "bm_header_inst*gfx950.s"))) i
         nlane = sum(1 for o, _ in body if LANE.match(o))
         fast, slow = classify(body)
         rows.append(("hdr", 0, fast + slow, slow, nbad, nlane))
+        bad += nbad > 0
+for sfile in sorted(glob.glob(os.path.join(build, "bm_header_hits_inst*gfx950.s"))) if HEADER_HITS else []:
+    for name in isa_loops.kernels(sfile, "header_hits_kernel"):
+        body = hot_block(sfile, name)
+        nbad = sum(1 for o, _ in body if BAD.match(o))
+        nlane = sum(1 for o, _ in body if LANE.match(o))
+        fast, slow = classify(body)
+        rows.append(("hdrh", 0, fast + slow, slow, nbad, nlane))
         bad += nbad > 0
 for tag, p, valu, slow, nbad, nlane in sorted(rows, key=lambda r: (len(r[0]), r[0], r[1])):
     if nbad or "-v" in sys.argv:
