@@ -88,6 +88,8 @@ U32_MAX = (1 << 32) - 1
 U256_MAX = (1 << 256) - 1
 BM_MAX_HEADER_HASHES = 1 << 24
 BM_MAX_HEADER_HITS = 1 << 20
+BM_MAX_HEADER_VERSIONS = 64
+BIP320_MASK = 0x1fffe000  # the version bits BIP 320 leaves to the miner
 
 
 class HeaderHit(ctypes.Structure):
@@ -97,6 +99,11 @@ class HeaderHit(ctypes.Structure):
 class HeaderHitsResult(ctypes.Structure):
     _fields_ = [("hash", ctypes.c_uint8 * 32), ("nonce", c_u32), ("reserved", c_u32), ("count", c_u64),
                 ("stored", c_u64)]
+
+
+class HeaderVersionsResult(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("nonce", c_u32), ("version_index", c_u32), ("version", c_u32),
+                ("found", c_i32)]
 
 
 class Segment(ctypes.Structure):
@@ -176,6 +183,8 @@ def _open(path):
         "bm_search_header_gpu": ([vp, ctypes.c_char_p, c_u32, c_u32, ctypes.c_char_p, P(HeaderResult)], ctypes.c_int),
         "bm_search_header_hits_gpu": ([vp, ctypes.c_char_p, c_u32, c_u32, ctypes.c_char_p, P(HeaderHit),
                                        ctypes.c_size_t, P(HeaderHitsResult)], ctypes.c_int),
+        "bm_search_header_versions_gpu": ([vp, ctypes.c_char_p, P(c_u32), ctypes.c_size_t, c_u32, c_u32,
+                                           ctypes.c_char_p, P(HeaderVersionsResult)], ctypes.c_int),
         "bm_header_hash_gpu": ([vp, ctypes.c_char_p, P(c_u32), ctypes.c_size_t, P(ctypes.c_uint8)], ctypes.c_int),
         "bm_header_target_from_bits": ([c_u32, P(ctypes.c_uint8)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
@@ -267,6 +276,29 @@ def bits_to_target(nbits: int) -> int:
     if load().bm_header_target_from_bits(nbits, buf) != BM_OK:
         raise ValueError(f"bits {nbits:#010x} is negative or overflows 256 bits")
     return int.from_bytes(bytes(buf), "big")
+
+
+def roll_versions(base: int, count: int, mask: int = BIP320_MASK):
+    """`count` version fields rolled from `base` inside `mask` (BIP 320's by
+    default): the i-th is base with the bits of i deposited into the mask's
+    bit positions, lowest first (base's own bits under the mask are replaced).
+    ValueError when count exceeds the
+    2^popcount(mask) values the mask holds."""
+    for v, what in ((base, "base"), (mask, "mask")):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U32_MAX:
+            raise ValueError(f"{what} must be in 0..2^32-1, got {v!r}")
+    if not isinstance(count, int) or isinstance(count, bool) or count < 0:
+        raise ValueError(f"count must be a non-negative integer, got {count!r}")
+    positions = [b for b in range(32) if mask >> b & 1]
+    if count > 1 << len(positions):
+        raise ValueError(f"mask {mask:#010x} holds {1 << len(positions)} versions, {count} asked for")
+    out = []
+    for i in range(count):
+        v = base & ~mask
+        for k, b in enumerate(positions):
+            v |= (i >> k & 1) << b
+        out.append(v)
+    return out
 
 
 def _header_bytes(header) -> bytes:
@@ -447,6 +479,29 @@ class Context:
         check(self._lib.bm_search_header_gpu(self.handle, header, nonce_lo, nonce_hi, tgt, ctypes.byref(r)),
               "bm_search_header_gpu")
         return bool(r.found), int.from_bytes(bytes(r.hash), "big"), r.nonce
+
+    def search_header_versions(self, header: bytes, versions, nonce_lo: int = 0, nonce_hi: int = U32_MAX,
+                               target=U256_MAX):
+        """Bitcoin block header under each of `versions` (1..64 version
+        fields; the header's own bytes 0..3 are ignored): the smallest nonce of
+        [nonce_lo, nonce_hi] at which any version's double SHA-256 is <=
+        target, and the smallest index among the versions that hit there ->
+        (True, hash, nonce, version_index); none -> (False, hash, nonce,
+        version_index) of the best share, the minimum of (hash >> 192, nonce,
+        index).  An empty range gives (False, 2^256-1, 2^32-1, 0)."""
+        header = _header_bytes(header)
+        versions = list(versions)
+        if not 1 <= len(versions) <= BM_MAX_HEADER_VERSIONS:
+            raise ValueError(f"1..{BM_MAX_HEADER_VERSIONS} versions, got {len(versions)}")
+        for v, what in [(nonce_lo, "nonce_lo"), (nonce_hi, "nonce_hi")] + [(v, "a version") for v in versions]:
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U32_MAX:
+                raise ValueError(f"{what} must be in 0..2^32-1, got {v!r}")
+        tgt = _target_bytes(target)
+        arr = (c_u32 * len(versions))(*versions)
+        r = HeaderVersionsResult()
+        check(self._lib.bm_search_header_versions_gpu(self.handle, header, arr, len(versions), nonce_lo, nonce_hi,
+                                                      tgt, ctypes.byref(r)), "bm_search_header_versions_gpu")
+        return bool(r.found), int.from_bytes(bytes(r.hash), "big"), r.nonce, r.version_index
 
     def search_header_hits(self, header: bytes, nonce_lo: int = 0, nonce_hi: int = U32_MAX, target=U256_MAX,
                            cap: int = 4096):

@@ -192,6 +192,10 @@ void read_env(bm_ctx* ctx) {
         if (end != e && *end == '\0' && errno == 0 && v <= kMaxTailNonces) ctx->tail_nonces = v;
     }
     if (const char* e = std::getenv("BTCMINER_PADC")) ctx->padc = std::strcmp(e, "0") != 0;
+    if (const char* e = std::getenv("BTCMINER_HEADER_GROUP")) {
+        const int v = std::atoi(e);
+        if (v == 1 || v == 2 || v == 4) ctx->header_group = v;
+    }
     if (const char* e = std::getenv("BTCMINER_CHUNK")) {
         char* end = nullptr;
         errno = 0;

@@ -3,7 +3,9 @@
 // built from the SHA-256 pieces of bm_kernels.hpp.  Two build units:
 // bm_header_inst.hip (header_kernel, header_hash_kernel) and
 // bm_header_hits_inst.hip (header_hits_kernel: header_kernel's body in hits
-// mode; the two share bm_header_body.inc).
+// mode; the two share bm_header_body.inc).  A third unit,
+// bm_header_versions_inst.hip, takes only the pieces (BM_HEADER_PIECES_ONLY)
+// for its own header_versions_kernel<M>.
 //
 // header_kernel, per nonce n (bm_header.hpp has the per-call host part):
 //   * W3 = bswap32(n).  n = (task << 8) | j: the task part is per lane, the
@@ -141,7 +143,9 @@ BM_DEV bool le256(const uint32_t (&h)[8], const uint32_t (&t)[8]) {
 // 64 * chunk_m consecutive tasks from the launch's counter (one returning
 // atomic per chunk, lane 0), lane l taking tasks base + l, base + 64 + l, ...
 // The body is bm_header_body.inc, shared with header_hits_kernel.
-#ifdef BM_HEADER_HITS_UNIT
+#if defined(BM_HEADER_PIECES_ONLY)
+// bm_header_versions_inst.hip: the pieces above, none of the kernels below.
+#elif defined(BM_HEADER_HITS_UNIT)
 // header_kernel in hits mode (bm_search_header_hits_gpu), the one kernel of
 // its build unit (bm_header_hits_inst.hip defines BM_HEADER_HITS_UNIT), so the
 // unit of the two kernels below holds what it always held.  Occupancy request

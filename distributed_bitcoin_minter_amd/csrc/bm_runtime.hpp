@@ -2,7 +2,7 @@
 // public interface is include/btcminer.h):
 //   bm_ctx.cpp     contexts and devices: lifetime, buffers, knobs, the rank join
 //   bm_combine.cpp the combine of a search's partials (RCCL allgather or host copies)
-//   bm_search.cpp  the five searches: kernel tables, sizing, enqueue, statistics
+//   bm_search.cpp  the six searches: kernel tables, sizing, enqueue, statistics
 //   bm_aux.hip     the only unit with device code: the kernels of bm_aux_kernels.hpp,
 //                  a host wrapper that launches the reduction, and the entry points
 //                  built on them (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu)
@@ -24,6 +24,7 @@
 
 #include "bm_common.h"
 #include "bm_header.hpp"
+#include "bm_header_versions.hpp"
 #include "bm_plan.hpp"
 #include "btcminer.h"
 
@@ -106,17 +107,18 @@ struct DeviceCtx {
     double wall_clock_hz = 100e6;                  // s_memrealtime rate
 };
 
-// The five searches share one plan -> enqueue -> combine -> stats path
+// The six searches share one plan -> enqueue -> combine -> stats path
 // (bm_search.cpp); a Mode says which one a call is, and carries what its
 // kernels take beyond a launch's own arguments.  DESIGN.md section 1, "Host
 // runtime layout", lists what a mode changes.
-enum class Kind { Search, Target, Hits, Header, HeaderHits };
+enum class Kind { Search, Target, Hits, Header, HeaderHits, HeaderVersions };
 struct Mode {
     Kind kind = Kind::Search;
     uint64_t target = 0;  // Target, Hits: the 64-bit bound (Header, HeaderHits: their 256-bit target is in HeaderArgs)
     uint64_t cap = 0;     // Hits, HeaderHits: entries of the hit buffer
     // first hit wins: launches in ascending nonce order, one hit word per device
-    bool first_hit() const { return kind == Kind::Target || kind == Kind::Header; }
+    // (HeaderVersions: the word holds a (nonce, version index) key, shared by the device's group launches)
+    bool first_hit() const { return kind == Kind::Target || kind == Kind::Header || kind == Kind::HeaderVersions; }
     // every hit: a counter and a buffer of 16-byte entries per device (d_hcount, d_hbuf)
     bool every_hit() const { return kind == Kind::Hits || kind == Kind::HeaderHits; }
     // a block-header call: one launch of HeaderArgs per device
@@ -130,6 +132,7 @@ struct Launch {
     union {
         SearchArgs search;  // Search, Target, Hits
         HeaderArgs header;  // Header, HeaderHits
+        HeaderVersionsArgs<kMaxVersionSlots> versions;  // HeaderVersions: a launch of M slots reads the first M
     } args;                 // the kernel's first parameter, by value
     uint64_t first_nonce;  // the lowest nonce it scans
     uint64_t tasks;        // what its work counter runs up to
@@ -250,13 +253,16 @@ struct bm_ctx {
     uint64_t lane_chunk = bm::kNoncesPerLaneChunk;  // nonces per lane per dequeue, at most (BTCMINER_CHUNK)
     std::vector<uint32_t> shares;  // the partitioner's shares per slot (empty: near-equal pieces)
     bool balance = false;          // multi-device: shares follow each device's measured rate
+    int header_group = bm::kMaxVersionSlots;  // bm_search_header_versions_gpu: versions per launch, at most (1, 2, 4;
+                                          // BTCMINER_HEADER_GROUP; DESIGN.md "Version rolling")
     bool padc = true;              // use search_kernel_padc / _padk where they apply (BTCMINER_PADC=0: never; A/B knob)
     // rank ctx: a join whose caller timed out while its worker was still
     // inside RCCL (the worker aborts the communicator if it ever gets one)
     std::shared_ptr<bm::JoinJob> pending_join;
     std::thread pending_worker;
     bm_stats_t stats;
-    bm_target_stats_t tstats;  // the last bm_search_target_gpu / bm_search_header_gpu (zero after a failed one)
+    bm_target_stats_t tstats;  // the last bm_search_target_gpu / bm_search_header_gpu / bm_search_header_versions_gpu
+                               // (zero after a failed one)
     bm::SubmitPool submit;  // multi-device: one submission thread per device but the first (last member:
                             // stopped first, when every device is idle)
 };

@@ -1,6 +1,6 @@
-// bm_search.cpp -- the five searches of include/btcminer.h (bm_search_gpu,
+// bm_search.cpp -- the six searches of include/btcminer.h (bm_search_gpu,
 // bm_search_target_gpu, bm_search_hits_gpu, bm_search_header_gpu,
-// bm_search_header_hits_gpu) over one path: plan and size every launch, enqueue each device's launches and its
+// bm_search_header_hits_gpu, bm_search_header_versions_gpu) over one path: plan and size every launch, enqueue each device's launches and its
 // second-pass reduction, combine the devices' partials, record the stats.
 // What differs between them is a Mode (bm_runtime.hpp) and the code around
 // that path in each *_impl.  Plain C++ over the HIP host API.
@@ -36,6 +36,8 @@ const void* g_hits[2][64];
 const void* g_header_search = nullptr;
 // header_hits_kernel, filled by bm_header_hits_inst.hip at load time
 const void* g_header_hits = nullptr;
+// header_versions_kernel<M> at [M], M = 1, 2, 4, filled by bm_header_versions_inst.hip at load time
+const void* g_header_versions[kMaxVersionSlots + 1];
 
 // Balance (bm_ctx_set_balance): a device's rate is measured only when its
 // piece held at least this many nonces (about 20 ms of one MI355X), and the
@@ -68,6 +70,10 @@ extern "C" void bm_register_header_kernels(const void* search_fn, const void* ha
 }
 
 extern "C" void bm_register_header_hits_kernel(const void* fn) { bm::g_header_hits = fn; }
+
+extern "C" void bm_register_header_versions_kernel(int m, const void* fn) {
+    if (m >= 1 && m <= bm::kMaxVersionSlots) bm::g_header_versions[m] = fn;
+}
 
 namespace bm {
 namespace {
@@ -203,6 +209,35 @@ int size_header_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const HeaderArgs& b
     return BM_OK;
 }
 
+// One device's launch of header_versions_kernel<m> (HeaderVersions): its piece
+// [lo, hi] of the nonce range for the m versions of one group (base holds
+// their terms), in tasks of 256 nonces of m hashes each.
+int size_versions_launch(bm_ctx* ctx, DeviceCtx& d, const HeaderVersionsArgs<kMaxVersionSlots>& base, int m,
+                         uint32_t lo, uint32_t hi, uint32_t part_off, Launch& L) {
+    const void* fn = g_header_versions[m];
+    if (!fn) return BM_EINTERNAL;
+    std::memset(&L, 0, sizeof L);
+    HeaderVersionsArgs<kMaxVersionSlots>& A = L.args.versions;
+    A = base;
+    A.lo = lo;
+    A.hi = hi;
+    A.t0 = lo >> kHeaderTaskBits;
+    A.ntask = (hi >> kHeaderTaskBits) - A.t0 + 1;
+    const LaunchGeometry g = launch_geometry(A.ntask, kHeaderTaskNonces, ctx->lane_chunk,
+                                             resident_blocks(ctx, d, fn), kBlock);
+    A.chunk_m = g.chunk_m;
+    A.part_off = part_off;
+    L.fn = fn;
+    L.first_nonce = lo;
+    L.tasks = A.ntask;
+    L.task_nonces = (uint64_t)kHeaderTaskNonces * (uint64_t)m;  // (nonce, version) pairs
+    L.stat.nbv = m;
+    L.stat.nonces = ((uint64_t)hi - lo + 1) * (uint64_t)m;
+    L.stat.grid = g.grid;
+    L.stat.tasks_per_thread = (uint32_t)g.tasks_per_thread;
+    return BM_OK;
+}
+
 // This process's piece of [lower, upper] (rank contexts: every rank passes the
 // same range and scans its contiguous share of it), split over the devices
 // (the partitioner: slot_pieces over ctx->shares; an empty piece has lo > hi).
@@ -268,6 +303,43 @@ int plan_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* msg, size_t len,
             BM_TRY(base ? size_header_launch(ctx, d, mode.kind, *base, (uint32_t)pieces[di].lo,
                                              (uint32_t)pieces[di].hi, L)
                         : size_launch(ctx, d, mode.kind, segs[i], off, L));
+            L.stat.device = (int)di;
+            off += L.stat.grid;
+            launches[di].push_back(L);
+        }
+        BM_TRY(ensure_buffers(d, mode, launches[di]));
+    }
+    return BM_OK;
+}
+
+// Stage 1 of a version-rolling search: every device gets one launch per group
+// of versions over its piece of the nonce range, in group order (they all
+// start at the piece's first nonce, so enqueue_device keeps that order).
+int plan_versions_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* header, const uint32_t* versions,
+                           size_t nver, const uint8_t* target, uint32_t lo, uint32_t hi,
+                           std::vector<std::vector<Launch>>& launches) {
+    uint8_t sizes[BM_MAX_HEADER_VERSIONS];
+    const int ngroups = host::versions_groups(nver, ctx->header_group, sizes);
+    std::vector<HeaderVersionsArgs<kMaxVersionSlots>> groups((size_t)ngroups);
+    size_t at = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        std::memset(&groups[g], 0, sizeof groups[g]);
+        // the shared schedule terms do not depend on the version: a kernel may share them
+        if (!host::header_versions_precompute(header, versions, at, sizes[g], groups[g])) return BM_EINTERNAL;
+        for (int i = 0; i < 8; ++i) groups[g].tgt[i] = host::load_be32(target + 4 * i);
+        at += sizes[g];
+    }
+    const std::vector<Piece> pieces = plan_pieces(ctx, lo, hi);
+    ctx->stats.nonces *= nver;  // pairs
+    for (size_t di = 0; di < pieces.size(); ++di) {
+        if (pieces[di].lo > pieces[di].hi) continue;
+        DeviceCtx& d = ctx->devs[di];
+        BM_HIP(hipSetDevice(d.id));
+        uint32_t off = 0;
+        for (int g = 0; g < ngroups; ++g) {
+            Launch L;
+            BM_TRY(size_versions_launch(ctx, d, groups[g], sizes[g], (uint32_t)pieces[di].lo,
+                                        (uint32_t)pieces[di].hi, off, L));
             L.stat.device = (int)di;
             off += L.stat.grid;
             launches[di].push_back(L);
@@ -346,6 +418,7 @@ int enqueue_device(bm_ctx* ctx, int di, const Mode& mode, std::vector<Launch>& l
             case Kind::Target: more({&target, &d.d_hit}); break;
             case Kind::Hits: more({&target, &d.d_hcount, &d.d_hbuf, &cap}); break;
             case Kind::Header: more({&d.d_hit}); break;
+            case Kind::HeaderVersions: more({&d.d_hit}); break;
             case Kind::HeaderHits: more({&d.d_hcount, &d.d_hbuf, &cap}); break;
         }
         BM_HIP(hipLaunchKernel(L.fn, dim3(L.stat.grid), dim3(kBlock), params, 0, s));
@@ -831,6 +904,44 @@ int header_hits_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t h
     return BM_OK;
 }
 
+// bm_search_header_versions_gpu: header_impl for several version fields.  Every
+// device scans its piece of the nonce range once per group of versions; its
+// hit word holds the smallest (nonce, version index) key of all its launches.
+// The host takes the lowest device's hit (pieces ascend with the device
+// index), or else the minimum of the (top 64 bits, key) partials, and checks
+// it (header_versions_select).
+int header_versions_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* versions, size_t nver, uint32_t lo,
+                         uint32_t hi, const uint8_t* target, bm_header_versions_result_t* out) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const Mode mode{Kind::HeaderVersions};
+    begin_call(ctx, mode);
+    const int ndev = (int)ctx->devs.size();
+    if (lo > hi) {
+        std::memset(out, 0, sizeof *out);
+        std::memset(out->hash, 0xFF, sizeof out->hash);
+        out->nonce = 0xFFFFFFFFu;
+        out->version = versions[0];
+        return BM_OK;
+    }
+
+    std::vector<std::vector<Launch>> launches(ndev);
+    std::vector<uint32_t> first(ndev, 0);
+    Partial best{UINT64_MAX, UINT64_MAX};
+    int rc = guarded(
+        [&] { return plan_versions_launches(ctx, mode, header, versions, nver, target, lo, hi, launches); });
+    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
+    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
+    if (rc == BM_OK) rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
+    if (rc != BM_OK) return fail_call(ctx, rc);
+
+    const uint64_t hit = scan_hit_words(ctx, launches);
+    bm_header_versions_result_t r;
+    rc = host::header_versions_select(header, versions, nver, target, hit, best, &r);
+    if (rc != BM_OK) return fail_call(ctx, rc);
+    *out = r;
+    return BM_OK;
+}
+
 }  // namespace
 }  // namespace bm
 
@@ -889,6 +1000,21 @@ int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t non
     bm_header_hits_result_t r;
     int rc = bm::guarded(
         [&] { return bm::header_hits_impl(ctx, header, nonce_lo, nonce_hi, target, hits, cap, &r); });
+    if (rc == BM_OK) *out = r;
+    return rc;
+}
+
+int bm_search_header_versions_gpu(bm_ctx_t* ctx, const uint8_t* header, const uint32_t* versions, size_t nver,
+                                  uint32_t nonce_lo, uint32_t nonce_hi, const uint8_t* target,
+                                  bm_header_versions_result_t* out) {
+    if (!ctx || !header || !versions || !target || !out) return BM_EINVAL;
+    if (nver == 0 || nver > BM_MAX_HEADER_VERSIONS) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    bm::DeviceGuard guard;
+    bm_header_versions_result_t r;
+    int rc = bm::guarded([&] {
+        return bm::header_versions_impl(ctx, header, versions, nver, nonce_lo, nonce_hi, target, &r);
+    });
     if (rc == BM_OK) *out = r;
     return rc;
 }

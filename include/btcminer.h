@@ -342,6 +342,57 @@ int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t header[80], uint32_t 
                               const uint8_t target[32], bm_header_hit_t* hits, size_t cap,
                               bm_header_hits_result_t* out);
 
+/* ---- version rolling: one header under several version fields -------------
+ * After 2^32 nonces a miner changes the header, and the cheapest change is the
+ * version field (BIP 320: the bits of mask 0x1fffe000 are free).  The version
+ * lies in the header's first 64-byte block, so the second block's message
+ * schedule is the same for every version, and a kernel that runs several
+ * versions side by side computes it once per nonce (overt AsicBoost).
+ *
+ * H(i, n) is bm_search_header_gpu's H(n) of the header whose bytes 0..3 are
+ * le32(versions[i]).  Bytes 0..3 and 76..79 of the caller's header are ignored.
+ * bm_search_header_versions_gpu scans [nonce_lo, nonce_hi] for every version.
+ *   found = 1: the pair minimising (n, i) lexicographically among all pairs of
+ *     the range with i < nver and H(i, n) <= target: the smallest nonce at
+ *     which any version hits, then the smallest index.  A repeated version is
+ *     legal and loses the tie to its first occurrence.
+ *   found = 0: the whole range was scanned for every version; the pair
+ *     minimises (H(i, n) >> 192, n, i).
+ *   hash = H(version_index, nonce) in full, recomputed on the host, which also
+ *     checks the device's claim (BM_EINTERNAL if it does not hold).
+ *   nonce_lo > nonce_hi: found = 0, hash all 0xFF, nonce = 0xFFFFFFFF,
+ *     version_index = 0, version = versions[0].
+ * The result never depends on timing, residency, streams, BTCMINER_CHUNK,
+ * blocks per CU, the split or on how the versions are grouped into launches:
+ * the list is cut into groups of 4, 2 and 1 versions (BTCMINER_HEADER_GROUP =
+ * 1, 2 or 4 caps the group size), one launch per device and group, and all of
+ * a device's launches share its hit word, so a later group scans only up to the
+ * best hit so far.
+ * nver == 0, nver > BM_MAX_HEADER_VERSIONS or a NULL ctx, header, versions,
+ * target or out: BM_EINVAL.  A rank context with world > 1: BM_EINVAL.  On
+ * failure `out` is untouched and the context stays usable.
+ * Contexts: as for bm_search_header_gpu; the nonce range is split and every
+ * device runs every version over its piece; the combine is by host copies.
+ * bm_ctx_set_balance does not learn from these calls; bm_ctx_set_test_fault
+ * applies; bm_ctx_last_stats lists one launch per device and group (nonces =
+ * the piece's size times the group's versions); bm_ctx_last_target_stats
+ * counts (nonce, version) pairs in nonces_dispatched.
+ *
+ * Out of scope: share enumeration across versions; ntime, extranonce or merkle
+ * rolling; cancelling across devices; rank groups; the LSP server protocol. */
+#define BM_MAX_HEADER_VERSIONS 64
+typedef struct bm_header_versions_result {
+    uint8_t hash[32];       /* as bm_header_result_t: most significant byte first */
+    uint32_t nonce;
+    uint32_t version_index; /* index into versions[] */
+    uint32_t version;       /* versions[version_index] */
+    int32_t found;
+} bm_header_versions_result_t; /* 48 bytes */
+
+int bm_search_header_versions_gpu(bm_ctx_t* ctx, const uint8_t header[80], const uint32_t* versions, size_t nver,
+                                  uint32_t nonce_lo, uint32_t nonce_hi, const uint8_t target[32],
+                                  bm_header_versions_result_t* out);
+
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */
 int bm_hash_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,

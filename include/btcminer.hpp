@@ -142,6 +142,19 @@ class Context {
         check(bm_search_header_gpu(ctx_, header, nonce_lo, nonce_hi, target, &r), "bm_search_header_gpu");
         return r;
     }
+    // the same header under each of `versions` (1..BM_MAX_HEADER_VERSIONS version
+    // fields, bytes 0..3): the smallest nonce at which any version's hash is
+    // <= target, then the smallest index (found = 1), or the best share over
+    // all pairs (found = 0): bm_search_header_versions_gpu
+    bm_header_versions_result_t search_header_versions(const uint8_t header[80], const std::vector<uint32_t>& versions,
+                                                       uint32_t nonce_lo, uint32_t nonce_hi,
+                                                       const uint8_t target[32]) {
+        bm_header_versions_result_t r;
+        check(bm_search_header_versions_gpu(ctx_, header, versions.data(), versions.size(), nonce_lo, nonce_hi, target,
+                                            &r),
+              "bm_search_header_versions_gpu");
+        return r;
+    }
     // every n in [nonce_lo, nonce_hi] whose double SHA-256 is <= target,
     // ascending, into `hits` (resized to the result's `stored`: empty when
     // count > cap), plus the exact count and the range's best share:

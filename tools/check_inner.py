@@ -10,7 +10,16 @@ bm_header_inst unit), row "hdr", the same way; its per-nonce block is the loop
 block with the most VALU (its deepest loop is the rare path's wave scan for the
 64-bit atomicMin).
 --header-hits: check header_hits_kernel (the block-header share enumeration,
-the bm_header_hits_inst unit), row "hdrh", as --header does."""
+the bm_header_hits_inst unit), row "hdrh", as --header does.
+--header-versions: check header_versions_kernel<M> (the version-rolling header
+search, the bm_header_versions_inst unit), rows "hdrv1", "hdrv2", "hdrv4".  The
+per-nonce code of an M-slot kernel is several basic blocks, because the rare
+branch after each slot's compare splits it: every block of the per-nonce loop
+from its header to its back edge is summed (the rare paths are laid out behind
+the back edge; one that was not would show as a memory op, its atomic).  The
+row gives VALU per nonce and per hash, the slow / fast split, the issue slots
+per hash under DESIGN.md section 5's model, max(slow, (slow + fast) / 2), and the
+v_readlane (SGPR spills read back), scratch and memory ops in that code."""
 import glob
 import os
 import re
@@ -29,7 +38,8 @@ bad = 0
 rows = []
 HEADER = "--header" in sys.argv
 HEADER_HITS = "--header-hits" in sys.argv
-for sfile in sorted(glob.glob(os.path.join(build, "*gfx950.s"))) if not (HEADER or HEADER_HITS) else []:
+HEADER_VERSIONS = "--header-versions" in sys.argv
+for sfile in sorted(glob.glob(os.path.join(build, "*gfx950.s"))) if not (HEADER or HEADER_HITS or HEADER_VERSIONS) else []:
     for name in isa_loops.kernels(sfile, "search_kernel"):
         m = re.search(r"search_kernel(_padc|_padk)?ILi(\d+)ELi(\d+)E(?:Li(\d+)E)?", name)
         if not m:
@@ -85,7 +95,70 @@ for sfile in sorted(glob.glob(os.path.join(build, "bm_header_hits_inst*gfx950.s"
         fast, slow = classify(body)
         rows.append(("hdrh", 0, fast + slow, slow, nbad, nlane))
         bad += nbad > 0
-for tag, p, valu, slow, nbad, nlane in sorted(rows, key=lambda r: (len(r[0]), r[0], r[1])):
+
+
+def loop_blocks(sfile, name):
+    """The per-nonce loop's main line: the loop whose header block holds the
+    most VALU, its blocks in layout order from the header to the back edge."""
+    lines = isa_loops.kernels(sfile, name)[name]
+    order, blocks, owner, cur, pending = [], {}, {}, None, None
+    for l in lines:
+        m = re.match(r"^(\.LBB\d+_\d+):\s*(;.*)?$", l) or re.match(r"^; (%bb\.\d+):\s*(;.*)?$", l)
+        if m:
+            cur = pending = m.group(1)
+            order.append(cur)
+            blocks[cur] = []
+            note = m.group(2) or ""
+        elif pending and re.match(r"^\s*;", l):
+            note = l
+        else:
+            note = ""
+        if note and cur:
+            h = re.search(r"in Loop: Header=(BB\d+_\d+)", note)
+            if h:
+                owner[cur] = ".L" + h.group(1)
+            elif "This Loop Header" in note:
+                owner[cur] = cur
+        if m or note:
+            continue
+        s = l.strip()
+        if s and not s.startswith(";"):
+            pending = None
+        if cur and s and not s.startswith((";", ".")):
+            blocks[cur].append((s.split()[0], s))
+    valu = lambda b: sum(1 for o, _ in blocks[b] if o.startswith("v_"))
+    head = max((b for b in order if owner.get(b) == b), key=valu)
+    out = []
+    for b in order[order.index(head):]:
+        if owner.get(b) != head:
+            break
+        out.append(blocks[b])
+        if any(o.startswith(("s_branch", "s_cbranch")) and t.split()[-1] == head for o, t in blocks[b]):
+            return out
+    raise SystemExit(f"{name}: no back edge found behind {head}")
+
+
+VROWS = []
+for sfile in sorted(glob.glob(os.path.join(build, "bm_header_versions_inst*gfx950.s"))) if HEADER_VERSIONS else []:
+    for name in isa_loops.kernels(sfile, "header_versions_kernel"):
+        slots = int(re.search(r"header_versions_kernelILi(\d+)E", name).group(1))
+        main = loop_blocks(sfile, name)
+        body = [op for blk in main for op in blk]
+        nbad = sum(1 for o, _ in body if BAD.match(o))
+        nread = sum(1 for o, _ in body if o.startswith("v_readlane"))
+        nlane = sum(1 for o, _ in body if LANE.match(o))
+        fast, slow = classify(body)
+        rows.append((f"hdrv{slots}", 0, fast + slow, slow, nbad, nlane))
+        VROWS.append((slots, fast, slow, nbad, nread, nlane - nread,
+                      "+".join(str(sum(classify(blk))) for blk in main if sum(classify(blk)) >= 100)))
+        bad += nbad > 0
+for slots, fast, slow, nbad, nread, nwrite, split in sorted(VROWS) if "-v" in sys.argv else []:
+    valu = fast + slow
+    print(f" 0:hdrv{slots} inner VALU={valu} slow={slow} fast={fast} VALU/hash={valu / slots:.1f} "
+          f"slots/hash={max(slow, (slow + fast) / 2) / slots:.1f} mem={nbad} readlane={nread} writelane={nwrite} "
+          f"blocks={split}")
+rows_printed = [r for r in rows if not r[0].startswith("hdrv") or r[4]]
+for tag, p, valu, slow, nbad, nlane in sorted(rows_printed, key=lambda r: (len(r[0]), r[0], r[1])):
     if nbad or "-v" in sys.argv:
         print(f"{p:2d}:{tag:3s} inner VALU={valu} slow={slow} mem={nbad} lane-spill={nlane}")
 print(f"{len(rows)} kernels checked, {bad} with scratch/memory ops in the inner loop, "
