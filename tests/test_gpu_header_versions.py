@@ -5,7 +5,9 @@ H(i, n) = sha256d(le32(versions[i]) || header[4:76] || le32(n)) as a
 little-endian 256-bit integer.  found: the pair minimising (n, i) among the
 hits; not found: the pair minimising (H >> 192, n, i).  Every hashlib window
 holds at most 2^16 nonces and 9 versions (the multi-device window the issue
-asks for, 3 * 2^15 nonces, holds 3), computed once and shared."""
+asks for, 3 * 2^15 nonces, holds 3), computed once and shared.  H, column,
+pairs, smallest and expect take the genesis header unless given another
+(test_other_headers: at most 5 * 2^13 pairs per case)."""
 import ctypes
 import functools
 import hashlib
@@ -13,6 +15,7 @@ import heapq
 import io
 import json
 import os
+import random
 import struct
 import subprocess
 import sys
@@ -35,41 +38,41 @@ LOW = (0, 65535)
 NVERS = (1, 2, 3, 4, 5, 7, 9)  # groups 1, 2, 2+1, 4, 4+1, 4+2+1, 4+4+1
 
 
-def H(version: int, nonce: int) -> int:
-    d = hashlib.sha256(struct.pack("<I", version) + GENESIS[4:76] + struct.pack("<I", nonce)).digest()
+def H(version: int, nonce: int, header: bytes = GENESIS) -> int:
+    d = hashlib.sha256(struct.pack("<I", version) + header[4:76] + struct.pack("<I", nonce)).digest()
     return int.from_bytes(hashlib.sha256(d).digest(), "little")
 
 
 @functools.lru_cache(maxsize=None)
-def column(version: int, lo: int, hi: int):
+def column(version: int, lo: int, hi: int, header: bytes = GENESIS):
     """(H(version, n)) for n in [lo, hi], computed once and never changed (a
-    piece of LOW is cut from LOW's)."""
-    if (lo, hi) != LOW and LOW[0] <= lo and hi <= LOW[1]:
+    piece of the genesis header's LOW is cut from LOW's)."""
+    if header == GENESIS and (lo, hi) != LOW and LOW[0] <= lo and hi <= LOW[1]:
         return column(version, *LOW)[lo:hi + 1]
-    return tuple(H(version, n) for n in range(lo, hi + 1))
+    return tuple(H(version, n, header) for n in range(lo, hi + 1))
 
 
-def pairs(versions, lo, hi):
+def pairs(versions, lo, hi, header: bytes = GENESIS):
     """Every (h, n, i) of the window, in (n, i) order."""
-    cols = [column(v, lo, hi) for v in versions]
+    cols = [column(v, lo, hi) if header == GENESIS else column(v, lo, hi, header) for v in versions]
     return [(cols[i][n - lo], n, i) for n in range(lo, hi + 1) for i in range(len(versions))]
 
 
 @functools.lru_cache(maxsize=None)
-def smallest(versions, lo, hi, count=100):
+def smallest(versions, lo, hi, count=100, header: bytes = GENESIS):
     """The window's `count` smallest (h, n, i), ascending."""
-    return tuple(heapq.nsmallest(count, pairs(versions, lo, hi)))
+    return tuple(heapq.nsmallest(count, pairs(versions, lo, hi, header)))
 
 
 @functools.lru_cache(maxsize=None)
-def expect(versions, lo, hi, target):
+def expect(versions, lo, hi, target, header: bytes = GENESIS):
     """What bm_search_header_versions_gpu must return, from hashlib."""
-    p = pairs(versions, lo, hi)
+    p = pairs(versions, lo, hi, header)
     hit = next(((True, h, n, i) for h, n, i in p if h <= target), None)  # p ascends in (n, i)
     if hit is not None:
         return hit
     _, n, i = min((h >> 192, n, i) for h, n, i in p)
-    return (False, H(versions[i], n), n, i)
+    return (False, H(versions[i], n, header), n, i)
 
 
 # ---- 1. known answer ---------------------------------------------------------
@@ -233,6 +236,120 @@ def test_top_window(gpu_ctx):
     # no wrap past 2^32-1: the whole window, and nothing else, is scanned
     assert gpu_ctx.search_header_versions(GENESIS, VERS4, lo, hi, 0) == expect(VERS4, lo, hi, 0)
     assert gpu_ctx.last_target_stats().nonces_dispatched == 65536 * 4
+
+
+def _edge_cases(vs):
+    """[(versions, lo, hi, target, want, pairs dispatched or None)]: what
+    test_empty_and_single_ranges and test_top_window assert, for any list."""
+    nver = len(vs)
+    cases = [(vs, 5, 4, U256, (False, U256, U32, 0), 0), (vs, U32, 0, 0, (False, U256, U32, 0), 0)]
+    for n in (0, 255, 256, U32):
+        hs = [H(v, n) for v in vs]
+        _, i = min((h >> 192, i) for i, h in enumerate(hs))
+        cases.append((vs, n, n, U256, (True, hs[0], n, 0), None))
+        cases.append((vs, n, n, 0, (False, hs[i], n, i), nver))
+        cases.append((vs, n, n, min(hs), (True, min(hs), n, hs.index(min(hs))), None))
+        cases.append((vs, n, n, min(hs) - 1, (False, hs[i], n, i), nver))
+    lo, hi = GOLDEN["genesis_windows"]["top"]["range"]
+    assert (lo, hi) == (2 ** 32 - 2 ** 16, U32)
+    T = smallest(vs, lo, hi)[2][0]
+    cases.append((vs, lo, hi, T, expect(vs, lo, hi, T), None))
+    # no wrap past 2^32-1: the whole window, and nothing else, is scanned
+    cases.append((vs, lo, hi, 0, expect(vs, lo, hi, 0), 65536 * nver))
+    for c in cases[2:]:
+        assert c[4] == expect(*c[:4])
+    return cases
+
+
+@pytest.mark.parametrize("nver", [4, 2, 1])
+def test_edges_every_kernel(gpu_ctx, nver):
+    """The empty, single-nonce and top-of-range cases for M = 4, 2 and 1."""
+    for vs, lo, hi, T, want, dispatched in _edge_cases(VERS4[:nver]):
+        assert gpu_ctx.search_header_versions(GENESIS, vs, lo, hi, T) == want, (lo, hi, hex(T))
+        if dispatched is not None:
+            assert gpu_ctx.last_target_stats().nonces_dispatched == dispatched, (lo, hi, hex(T))
+        if lo <= hi:
+            assert gpu_ctx.last_stats().launches == 1
+
+
+_CHILD_EDGES = r"""
+import json, sys
+from distributed_bitcoin_minter_amd import Context
+header = bytes.fromhex(sys.argv[1])
+cases = json.loads(sys.argv[2])
+out = []
+with Context(num_gpus=1) as ctx:
+    for vs, lo, hi, t in cases:
+        f, h, n, i = ctx.search_header_versions(header, vs, lo, hi, int(t, 16))
+        out.append([f, format(h, "x"), n, i, ctx.last_target_stats().nonces_dispatched, ctx.last_stats().launches])
+print(json.dumps(out))
+"""
+
+
+def test_edges_one_version_per_launch():
+    """The same cases under BTCMINER_HEADER_GROUP=1, in one fresh child: every
+    list runs as launches of the M = 1 kernel."""
+    cases = [c for nver in (4, 2, 1) for c in _edge_cases(VERS4[:nver])]
+    arg = json.dumps([[list(vs), lo, hi, format(T, "x")] for vs, lo, hi, T, _, _ in cases])
+    r = subprocess.run([sys.executable, "-c", _CHILD_EDGES, GENESIS.hex(), arg], capture_output=True, text=True,
+                       timeout=120, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT, BTCMINER_HEADER_GROUP="1"))
+    assert r.returncode == 0, r.stderr
+    got = json.loads(r.stdout)
+    assert len(got) == len(cases)
+    for (vs, lo, hi, T, want, dispatched), (f, h, n, i, disp, launches) in zip(cases, got):
+        assert (bool(f), int(h, 16), n, i) == want, (vs, lo, hi, hex(T))
+        if dispatched is not None:
+            assert disp == dispatched, (vs, lo, hi, hex(T))
+        if lo <= hi:
+            assert launches == len(vs)
+
+
+# ---- 6b. other headers ---------------------------------------------------------
+
+def _other_headers():
+    rng = random.Random(0xC0DE)
+    return [bytes(rng.getrandbits(8) for _ in range(80)) for _ in range(4)] + [b"\x00" * 80, b"\xff" * 80]
+
+
+OTHER_VERSIONS = ((0, 0xffffffff, 0x20000000, 1),                   # one launch of 4
+                  (0x3fffe000, 0, 2, 0xffffffff, 0x20004000),       # 4 + 1
+                  (0xffffffff, 0x1fffe000, 0))                      # 2 + 1
+
+
+def _other_cases():
+    """(header, versions, lo, hi, pick): six headers under three version lists
+    each, ranges of at most 2^13 nonces (at most 5 * 2^13 pairs), a third
+    starting at 0, a third ending at 2^32-1, the rest anywhere."""
+    assert all(set(vs) <= set(VERS9) and {0, 0xffffffff} <= set(vs) for vs in OTHER_VERSIONS)
+    rng = random.Random(0x0715)
+    cases = []
+    for hi_, header in enumerate(_other_headers()):
+        for vi, vs in enumerate(OTHER_VERSIONS):
+            k = 3 * hi_ + vi
+            length = [1, 255, 256, 257, 8192, 8191][k] if k < 6 else rng.randint(2, 8192)
+            where = (hi_ + vi) % 3
+            lo = 0 if where == 0 else U32 - length + 1 if where == 1 else rng.randint(1, U32 - length)
+            cases.append((header, vs, lo, lo + length - 1, rng.random()))
+    return cases
+
+
+@pytest.mark.parametrize("case", _other_cases(), ids=lambda c: f"{c[0][:2].hex()}-{len(c[1])}v-{c[2]}+{c[3] - c[2] + 1}")
+def test_other_headers(gpu_ctx, case):
+    """The shared schedule words (w16, w17, k18, k19, k31, k32) come from header
+    bytes 64..75: here they take other values than the genesis block's."""
+    header, vs, lo, hi, pick = case
+    nver, length = len(vs), hi - lo + 1
+    assert length <= 2 ** 13 and header[64:76] != GENESIS[64:76]
+    by_hash = smallest(vs, lo, hi, 50, header)
+    T = by_hash[int(pick * min(len(by_hash), 50))][0]  # one of the window's own 50 smallest pair hashes
+    want = expect(vs, lo, hi, T, header)
+    assert want[0]
+    assert gpu_ctx.search_header_versions(header, vs, lo, hi, T) == want
+    want = expect(vs, lo, hi, by_hash[0][0] - 1, header)
+    assert want == (False,) + by_hash[0]
+    assert gpu_ctx.search_header_versions(header, vs, lo, hi, by_hash[0][0] - 1) == want
+    assert gpu_ctx.last_target_stats().nonces_dispatched == length * nver
+    assert gpu_ctx.last_stats().launches == nver // 4 + (nver % 4) // 2 + nver % 2
 
 
 # ---- 7. independence from grouping and scheduling ------------------------------
