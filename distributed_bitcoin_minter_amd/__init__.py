@@ -10,10 +10,11 @@ re-built as gfx950 HIP kernels behind the C ABI in include/btcminer.h
         print(m.search("bradfitz", 0, 9999))   # (1419516646206828, 9898)
 """
 from . import bitcoin, dist
-from ._lib import (BtcMinerError, Context, HeaderHit, HeaderHitsResult, HeaderVersionsResult, HitsResult, LIB_PATH,
-                   bits_to_target, device_count, plan_segments, rccl_unique_id, roll_versions)
+from ._lib import (BtcMinerError, Context, HeaderHit, HeaderHitsResult, HeaderVersionHit, HeaderVersionsHitsResult,
+                   HeaderVersionsResult, HitsResult, LIB_PATH, bits_to_target, device_count, plan_segments,
+                   rccl_unique_id, roll_versions)
 from .miner import Miner
 
 __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", "HeaderHitsResult",
-           "HeaderVersionsResult", "HitsResult", "LIB_PATH", "bits_to_target", "device_count", "plan_segments",
-           "rccl_unique_id", "roll_versions"]
+           "HeaderVersionHit", "HeaderVersionsHitsResult", "HeaderVersionsResult", "HitsResult", "LIB_PATH",
+           "bits_to_target", "device_count", "plan_segments", "rccl_unique_id", "roll_versions"]

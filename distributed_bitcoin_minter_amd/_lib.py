@@ -106,6 +106,16 @@ class HeaderVersionsResult(ctypes.Structure):
                 ("found", c_i32)]
 
 
+class HeaderVersionHit(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("nonce", c_u32), ("version_index", c_u32), ("version", c_u32),
+                ("reserved", c_u32)]
+
+
+class HeaderVersionsHitsResult(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("nonce", c_u32), ("version_index", c_u32), ("version", c_u32),
+                ("reserved", c_u32), ("count", c_u64), ("stored", c_u64)]
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -185,6 +195,9 @@ def _open(path):
                                        ctypes.c_size_t, P(HeaderHitsResult)], ctypes.c_int),
         "bm_search_header_versions_gpu": ([vp, ctypes.c_char_p, P(c_u32), ctypes.c_size_t, c_u32, c_u32,
                                            ctypes.c_char_p, P(HeaderVersionsResult)], ctypes.c_int),
+        "bm_search_header_versions_hits_gpu": ([vp, ctypes.c_char_p, P(c_u32), ctypes.c_size_t, c_u32, c_u32,
+                                                ctypes.c_char_p, P(HeaderVersionHit), ctypes.c_size_t,
+                                                P(HeaderVersionsHitsResult)], ctypes.c_int),
         "bm_header_hash_gpu": ([vp, ctypes.c_char_p, P(c_u32), ctypes.c_size_t, P(ctypes.c_uint8)], ctypes.c_int),
         "bm_header_target_from_bits": ([c_u32, P(ctypes.c_uint8)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
@@ -502,6 +515,40 @@ class Context:
         check(self._lib.bm_search_header_versions_gpu(self.handle, header, arr, len(versions), nonce_lo, nonce_hi,
                                                       tgt, ctypes.byref(r)), "bm_search_header_versions_gpu")
         return bool(r.found), int.from_bytes(bytes(r.hash), "big"), r.nonce, r.version_index
+
+    def search_header_versions_hits(self, header: bytes, versions, nonce_lo: int = 0, nonce_hi: int = U32_MAX,
+                                    target=U256_MAX, cap: int = 65536):
+        """Bitcoin block header under each of `versions` (1..64 version fields):
+        every (nonce, version index) pair of [nonce_lo, nonce_hi] whose double
+        SHA-256 is <= target -> (count, hits, (best hash, best nonce, best
+        index)): hits is the list of (hash, nonce, index) ascending by (nonce,
+        index), or None when count > cap (nothing is returned then; count is
+        still exact); the best share is search_header_versions()'s answer at
+        target 0.  cap = 0 only counts.  An empty range gives
+        (0, [], (2^256-1, 2^32-1, 0))."""
+        header = _header_bytes(header)
+        versions = list(versions)
+        if not 1 <= len(versions) <= BM_MAX_HEADER_VERSIONS:
+            raise ValueError(f"1..{BM_MAX_HEADER_VERSIONS} versions, got {len(versions)}")
+        for v, what in [(nonce_lo, "nonce_lo"), (nonce_hi, "nonce_hi")] + [(v, "a version") for v in versions]:
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U32_MAX:
+                raise ValueError(f"{what} must be in 0..2^32-1, got {v!r}")
+        tgt = _target_bytes(target)
+        if not isinstance(cap, int) or isinstance(cap, bool) or not 0 <= cap <= BM_MAX_HEADER_HITS:
+            raise ValueError(f"cap must be in 0..{BM_MAX_HEADER_HITS}, got {cap!r}")
+        arr = (c_u32 * len(versions))(*versions)
+        r = HeaderVersionsHitsResult()
+        buf = (HeaderVersionHit * cap)() if cap > 0 else None
+        check(self._lib.bm_search_header_versions_hits_gpu(self.handle, header, arr, len(versions), nonce_lo,
+                                                           nonce_hi, tgt, buf, cap, ctypes.byref(r)),
+              "bm_search_header_versions_hits_gpu")
+        hits = None
+        if r.count <= cap:
+            size = ctypes.sizeof(HeaderVersionHit)
+            raw = ctypes.string_at(buf, size * r.stored) if buf is not None else b""
+            hits = [(int.from_bytes(raw[o:o + 32], "big"), int.from_bytes(raw[o + 32:o + 36], "little"),
+                     int.from_bytes(raw[o + 36:o + 40], "little")) for o in range(0, len(raw), size)]
+        return r.count, hits, (int.from_bytes(bytes(r.hash), "big"), r.nonce, r.version_index)
 
     def search_header_hits(self, header: bytes, nonce_lo: int = 0, nonce_hi: int = U32_MAX, target=U256_MAX,
                            cap: int = 4096):

@@ -107,20 +107,23 @@ struct DeviceCtx {
     double wall_clock_hz = 100e6;                  // s_memrealtime rate
 };
 
-// The six searches share one plan -> enqueue -> combine -> stats path
+// The seven searches share one plan -> enqueue -> combine -> stats path
 // (bm_search.cpp); a Mode says which one a call is, and carries what its
 // kernels take beyond a launch's own arguments.  DESIGN.md section 1, "Host
 // runtime layout", lists what a mode changes.
-enum class Kind { Search, Target, Hits, Header, HeaderHits, HeaderVersions };
+enum class Kind { Search, Target, Hits, Header, HeaderHits, HeaderVersions, HeaderVersionsHits };
 struct Mode {
     Kind kind = Kind::Search;
     uint64_t target = 0;  // Target, Hits: the 64-bit bound (Header, HeaderHits: their 256-bit target is in HeaderArgs)
-    uint64_t cap = 0;     // Hits, HeaderHits: entries of the hit buffer
+    uint64_t cap = 0;     // Hits, HeaderHits, HeaderVersionsHits: entries of the hit buffer
     // first hit wins: launches in ascending nonce order, one hit word per device
     // (HeaderVersions: the word holds a (nonce, version index) key, shared by the device's group launches)
     bool first_hit() const { return kind == Kind::Target || kind == Kind::Header || kind == Kind::HeaderVersions; }
     // every hit: a counter and a buffer of 16-byte entries per device (d_hcount, d_hbuf)
-    bool every_hit() const { return kind == Kind::Hits || kind == Kind::HeaderHits; }
+    // (HeaderVersionsHits: both shared by the device's group launches, the counter zeroed once)
+    bool every_hit() const {
+        return kind == Kind::Hits || kind == Kind::HeaderHits || kind == Kind::HeaderVersionsHits;
+    }
     // a block-header call: one launch of HeaderArgs per device
     bool header() const { return kind == Kind::Header || kind == Kind::HeaderHits; }
 };
@@ -132,7 +135,7 @@ struct Launch {
     union {
         SearchArgs search;  // Search, Target, Hits
         HeaderArgs header;  // Header, HeaderHits
-        HeaderVersionsArgs<kMaxVersionSlots> versions;  // HeaderVersions: a launch of M slots reads the first M
+        HeaderVersionsArgs<kMaxVersionSlots> versions;  // HeaderVersions, HeaderVersionsHits: a launch of M slots reads the first M
     } args;                 // the kernel's first parameter, by value
     uint64_t first_nonce;  // the lowest nonce it scans
     uint64_t tasks;        // what its work counter runs up to

@@ -1,6 +1,7 @@
-// bm_search.cpp -- the six searches of include/btcminer.h (bm_search_gpu,
+// bm_search.cpp -- the seven searches of include/btcminer.h (bm_search_gpu,
 // bm_search_target_gpu, bm_search_hits_gpu, bm_search_header_gpu,
-// bm_search_header_hits_gpu, bm_search_header_versions_gpu) over one path: plan and size every launch, enqueue each device's launches and its
+// bm_search_header_hits_gpu, bm_search_header_versions_gpu,
+// bm_search_header_versions_hits_gpu) over one path: plan and size every launch, enqueue each device's launches and its
 // second-pass reduction, combine the devices' partials, record the stats.
 // What differs between them is a Mode (bm_runtime.hpp) and the code around
 // that path in each *_impl.  Plain C++ over the HIP host API.
@@ -14,6 +15,7 @@
 #include <cstring>
 
 #include "bm_header_hits.hpp"
+#include "bm_header_versions_hits.hpp"
 #include "bm_runtime.hpp"
 
 namespace bm {
@@ -38,6 +40,8 @@ const void* g_header_search = nullptr;
 const void* g_header_hits = nullptr;
 // header_versions_kernel<M> at [M], M = 1, 2, 4, filled by bm_header_versions_inst.hip at load time
 const void* g_header_versions[kMaxVersionSlots + 1];
+// header_versions_hits_kernel<M> at [M], filled by bm_header_versions_hits_inst.hip at load time
+const void* g_header_versions_hits[kMaxVersionSlots + 1];
 
 // Balance (bm_ctx_set_balance): a device's rate is measured only when its
 // piece held at least this many nonces (about 20 ms of one MI355X), and the
@@ -73,6 +77,10 @@ extern "C" void bm_register_header_hits_kernel(const void* fn) { bm::g_header_hi
 
 extern "C" void bm_register_header_versions_kernel(int m, const void* fn) {
     if (m >= 1 && m <= bm::kMaxVersionSlots) bm::g_header_versions[m] = fn;
+}
+
+extern "C" void bm_register_header_versions_hits_kernel(int m, const void* fn) {
+    if (m >= 1 && m <= bm::kMaxVersionSlots) bm::g_header_versions_hits[m] = fn;
 }
 
 namespace bm {
@@ -209,12 +217,13 @@ int size_header_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const HeaderArgs& b
     return BM_OK;
 }
 
-// One device's launch of header_versions_kernel<m> (HeaderVersions): its piece
-// [lo, hi] of the nonce range for the m versions of one group (base holds
-// their terms), in tasks of 256 nonces of m hashes each.
-int size_versions_launch(bm_ctx* ctx, DeviceCtx& d, const HeaderVersionsArgs<kMaxVersionSlots>& base, int m,
-                         uint32_t lo, uint32_t hi, uint32_t part_off, Launch& L) {
-    const void* fn = g_header_versions[m];
+// One device's launch of header_versions_kernel<m> (HeaderVersions) or
+// header_versions_hits_kernel<m> (HeaderVersionsHits): its piece [lo, hi] of the
+// nonce range for the m versions of one group (base holds their terms), in
+// tasks of 256 nonces of m hashes each.
+int size_versions_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const HeaderVersionsArgs<kMaxVersionSlots>& base,
+                         int m, uint32_t lo, uint32_t hi, uint32_t part_off, Launch& L) {
+    const void* fn = (kind == Kind::HeaderVersionsHits ? g_header_versions_hits : g_header_versions)[m];
     if (!fn) return BM_EINTERNAL;
     std::memset(&L, 0, sizeof L);
     HeaderVersionsArgs<kMaxVersionSlots>& A = L.args.versions;
@@ -312,7 +321,7 @@ int plan_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* msg, size_t len,
     return BM_OK;
 }
 
-// Stage 1 of a version-rolling search: every device gets one launch per group
+// Stage 1 of a version-rolling search or enumeration: every device gets one launch per group
 // of versions over its piece of the nonce range, in group order (they all
 // start at the piece's first nonce, so enqueue_device keeps that order).
 int plan_versions_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* header, const uint32_t* versions,
@@ -338,7 +347,7 @@ int plan_versions_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* header,
         uint32_t off = 0;
         for (int g = 0; g < ngroups; ++g) {
             Launch L;
-            BM_TRY(size_versions_launch(ctx, d, groups[g], sizes[g], (uint32_t)pieces[di].lo,
+            BM_TRY(size_versions_launch(ctx, d, mode.kind, groups[g], sizes[g], (uint32_t)pieces[di].lo,
                                         (uint32_t)pieces[di].hi, off, L));
             L.stat.device = (int)di;
             off += L.stat.grid;
@@ -420,6 +429,7 @@ int enqueue_device(bm_ctx* ctx, int di, const Mode& mode, std::vector<Launch>& l
             case Kind::Header: more({&d.d_hit}); break;
             case Kind::HeaderVersions: more({&d.d_hit}); break;
             case Kind::HeaderHits: more({&d.d_hcount, &d.d_hbuf, &cap}); break;
+            case Kind::HeaderVersionsHits: more({&d.d_hcount, &d.d_hbuf, &cap}); break;
         }
         BM_HIP(hipLaunchKernel(L.fn, dim3(L.stat.grid), dim3(kBlock), params, 0, s));
         if (timed) BM_HIP(hipEventRecord(d.ev[2 * li + 1], s));
@@ -942,6 +952,86 @@ int header_versions_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* ver
     return BM_OK;
 }
 
+// bm_search_header_versions_hits_gpu: header_versions_impl's launches (one per
+// device and group of versions, over the partitioner's pieces) in hits mode,
+// with header_hits_impl's host side.  All of a device's launches append
+// {top 64 bits, (nonce << 32) | version index} to d_hbuf through d_hcount,
+// zeroed once before the device's first launch; the host reads every counter
+// back and, only when their sum fits in cap, the entries, which
+// header_versions_hits_collect sorts by (nonce, index), rehashes in full and
+// checks.  The best share is header_versions_impl's found = 0 answer.  hits
+// and out are written last, on success only.
+int header_versions_hits_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* versions, size_t nver,
+                              uint32_t lo, uint32_t hi, const uint8_t* target, bm_header_version_hit_t* hits,
+                              size_t cap, bm_header_versions_hits_result_t* out) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const Mode mode{Kind::HeaderVersionsHits, 0, (uint64_t)cap};
+    begin_call(ctx, mode);
+    const int ndev = (int)ctx->devs.size();
+    bm_header_versions_hits_result_t r;
+    std::memset(&r, 0, sizeof r);
+    if (lo > hi) {
+        std::memset(r.hash, 0xFF, sizeof r.hash);
+        r.nonce = 0xFFFFFFFFu;
+        r.version = versions[0];
+        *out = r;
+        return BM_OK;
+    }
+
+    std::vector<std::vector<Launch>> launches(ndev);
+    std::vector<uint32_t> first(ndev, 0);
+    std::vector<Partial> got;
+    std::vector<bm_header_version_hit_t> list;
+    Partial best{UINT64_MAX, UINT64_MAX};
+    int rc = guarded(
+        [&] { return plan_versions_launches(ctx, mode, header, versions, nver, target, lo, hi, launches); });
+    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
+    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
+    if (rc != BM_OK) return fail_call(ctx, rc);
+
+    uint64_t count = 0;
+    std::vector<size_t> counts(ndev, 0);
+    for (int di = 0; di < ndev; ++di) {
+        if (launches[di].empty()) continue;
+        const uint64_t c = *ctx->devs[di].h_hcount;
+        if (c > ctx->devs[di].piece_nonces * (uint64_t)nver) return fail_call(ctx, BM_EINTERNAL);  // a pair counts once
+        counts[di] = (size_t)c;
+        count += c;
+    }
+    if (count <= cap && count > 0) {
+        rc = guarded([&] {
+            got.resize((size_t)count);
+            list.resize((size_t)count);
+            size_t at = 0;
+            for (int di = 0; di < ndev; ++di) {
+                DeviceCtx& d = ctx->devs[di];
+                if (counts[di] == 0) continue;
+                BM_HIP(hipSetDevice(d.id));
+                BM_HIP(hipMemcpyAsync(got.data() + at, d.d_hbuf, counts[di] * sizeof(Partial), hipMemcpyDeviceToHost,
+                                      d.stream));
+                BM_HIP(hipStreamSynchronize(d.stream));
+                at += counts[di];
+            }
+            return host::header_versions_hits_collect(header, versions, nver, target, lo, hi, got.data(),
+                                                      counts.data(), ndev, list.data());
+        });
+        if (rc != BM_OK) return fail_call(ctx, rc);
+    }
+
+    // the best share: the device's claim against the host's hash of that pair, and against the count
+    rc = host::header_versions_hits_best(header, versions, nver, target, best, count, &r);
+    if (rc != BM_OK) return fail_call(ctx, rc);
+
+    rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
+    if (rc != BM_OK) return fail_call(ctx, rc);
+
+    r.count = count;
+    r.stored = count <= cap ? count : 0;
+    if (r.stored) std::memcpy(hits, list.data(), (size_t)r.stored * sizeof(bm_header_version_hit_t));
+    *out = r;
+    return BM_OK;
+}
+
 }  // namespace
 }  // namespace bm
 
@@ -1014,6 +1104,23 @@ int bm_search_header_versions_gpu(bm_ctx_t* ctx, const uint8_t* header, const ui
     bm_header_versions_result_t r;
     int rc = bm::guarded([&] {
         return bm::header_versions_impl(ctx, header, versions, nver, nonce_lo, nonce_hi, target, &r);
+    });
+    if (rc == BM_OK) *out = r;
+    return rc;
+}
+
+int bm_search_header_versions_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, const uint32_t* versions, size_t nver,
+                                       uint32_t nonce_lo, uint32_t nonce_hi, const uint8_t* target,
+                                       bm_header_version_hit_t* hits, size_t cap,
+                                       bm_header_versions_hits_result_t* out) {
+    if (!ctx || !header || !versions || !target || !out) return BM_EINVAL;
+    if (nver == 0 || nver > BM_MAX_HEADER_VERSIONS) return BM_EINVAL;
+    if (cap > BM_MAX_HEADER_HITS || (!hits && cap > 0)) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    bm::DeviceGuard guard;
+    bm_header_versions_hits_result_t r;
+    int rc = bm::guarded([&] {
+        return bm::header_versions_hits_impl(ctx, header, versions, nver, nonce_lo, nonce_hi, target, hits, cap, &r);
     });
     if (rc == BM_OK) *out = r;
     return rc;

@@ -378,8 +378,9 @@ int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t header[80], uint32_t 
  * the piece's size times the group's versions); bm_ctx_last_target_stats
  * counts (nonce, version) pairs in nonces_dispatched.
  *
- * Out of scope: share enumeration across versions; ntime, extranonce or merkle
- * rolling; cancelling across devices; rank groups; the LSP server protocol. */
+ * Share enumeration across versions is bm_search_header_versions_hits_gpu, below.
+ * Out of scope: ntime, extranonce or merkle rolling; cancelling across devices;
+ * rank groups; the LSP server protocol. */
 #define BM_MAX_HEADER_VERSIONS 64
 typedef struct bm_header_versions_result {
     uint8_t hash[32];       /* as bm_header_result_t: most significant byte first */
@@ -392,6 +393,66 @@ typedef struct bm_header_versions_result {
 int bm_search_header_versions_gpu(bm_ctx_t* ctx, const uint8_t header[80], const uint32_t* versions, size_t nver,
                                   uint32_t nonce_lo, uint32_t nonce_hi, const uint8_t target[32],
                                   bm_header_versions_result_t* out);
+
+/* ---- version-rolling shares: every (nonce, version) pair that meets a target
+ * bm_search_header_versions_hits_gpu scans all of [nonce_lo, nonce_hi] under
+ * every version (no early exit) and returns every pair (n, i), i < nver, with
+ * H(i, n) <= target, plus the best share over all pairs: what a pool miner with
+ * version rolling on submits.  H(i, n), `hash` and `target` are as for
+ * bm_search_header_versions_gpu: 256-bit numbers written MOST significant byte
+ * first, compared over the full 256 bits.
+ *   hits[0 .. stored) holds {H(i, n), n, i, versions[i], 0} for every hit,
+ *     ascending by (nonce, version_index), each pair exactly once (every hash
+ *     recomputed on the host).  A version that appears twice in the list yields
+ *     two entries with different indices.  count is exact, always.
+ *   All or nothing, as in bm_search_header_hits_gpu: count > cap writes NOTHING
+ *     to hits, stored = 0, and the call still succeeds with the exact count.
+ *   hits == NULL with cap == 0 is a pure count.  cap > BM_MAX_HEADER_HITS, or
+ *     hits == NULL with cap > 0: BM_EINVAL.
+ *   out->hash / nonce / version_index / version: the pair minimising
+ *     (H(i, n) >> 192, n, i), with its full hash: exactly the answer of
+ *     bm_search_header_versions_gpu at target 0.
+ *   nonce_lo > nonce_hi: count = stored = 0 and that call's empty answer: hash
+ *     all 0xFF, nonce = 0xFFFFFFFF, version_index = 0, version = versions[0];
+ *     hits untouched.
+ * nver == 0, nver > BM_MAX_HEADER_VERSIONS or a NULL ctx, header, versions,
+ * target or out: BM_EINVAL, before anything is dereferenced.  A rank context
+ * with world > 1: BM_EINVAL.  On any failure `hits` and `out` are untouched and
+ * the context stays usable (a device buffer that cannot grow to cap: BM_ENOMEM).
+ * The result never depends on timing, residency, streams, BTCMINER_CHUNK,
+ * blocks per CU, the split or the grouping (BTCMINER_HEADER_GROUP).
+ * Contexts: one device, or one process over several (a device listed N times
+ * included): the nonce range is cut by the partitioner, every device runs every
+ * group of versions over its piece, one launch of header_versions_hits_kernel<M>
+ * per device and group, all of a device's launches appending 16-byte entries
+ * {H(i, n) >> 192, (n << 32) | i} through one counter into one buffer; the host
+ * sorts them by (n, i), recomputes each full hash and checks the device's claim
+ * (BM_EINTERNAL if one fails) -- always by host copies.
+ * bm_ctx_set_balance does not learn from these calls; bm_ctx_set_test_fault
+ * applies; bm_ctx_last_stats lists one launch per device and group and counts
+ * (nonce, version) pairs in nonces; bm_ctx_last_target_stats is not touched.
+ * Cost: that of a full bm_search_header_versions_gpu scan while hits are rare.
+ *
+ * Out of scope: ntime, extranonce or merkle rolling; cancelling across devices;
+ * rank groups; the LSP server protocol. */
+typedef struct bm_header_version_hit {
+    uint8_t hash[32];        /* H(version_index, nonce), most significant byte first */
+    uint32_t nonce;
+    uint32_t version_index;  /* index into versions[] */
+    uint32_t version;        /* versions[version_index] */
+    uint32_t reserved;       /* 0 */
+} bm_header_version_hit_t;   /* 48 bytes */
+typedef struct bm_header_versions_hits_result {
+    uint8_t hash[32];        /* the best share over all pairs, in full */
+    uint32_t nonce, version_index, version, reserved;
+    uint64_t count;          /* pairs (n, i), n in [lo, hi], i < nver, H(i, n) <= target: exact, always */
+    uint64_t stored;         /* entries written to hits[]: count when count <= cap, else 0 */
+} bm_header_versions_hits_result_t; /* 64 bytes */
+
+int bm_search_header_versions_hits_gpu(bm_ctx_t* ctx, const uint8_t header[80], const uint32_t* versions,
+                                       size_t nver, uint32_t nonce_lo, uint32_t nonce_hi, const uint8_t target[32],
+                                       bm_header_version_hit_t* hits, size_t cap,
+                                       bm_header_versions_hits_result_t* out);
 
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */

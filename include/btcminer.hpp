@@ -170,6 +170,25 @@ class Context {
         hits = std::move(buf);
         return r;
     }
+    // every (n, i), n in [nonce_lo, nonce_hi], whose double SHA-256 under
+    // versions[i] is <= target, ascending by (n, i), into `hits` (resized to the
+    // result's `stored`: empty when count > cap), plus the exact count and the
+    // best share over all pairs: bm_search_header_versions_hits_gpu
+    bm_header_versions_hits_result_t search_header_versions_hits(const uint8_t header[80],
+                                                                 const std::vector<uint32_t>& versions,
+                                                                 uint32_t nonce_lo, uint32_t nonce_hi,
+                                                                 const uint8_t target[32],
+                                                                 std::vector<bm_header_version_hit_t>& hits,
+                                                                 size_t cap) {
+        bm_header_versions_hits_result_t r;
+        std::vector<bm_header_version_hit_t> buf(cap);
+        check(bm_search_header_versions_hits_gpu(ctx_, header, versions.data(), versions.size(), nonce_lo, nonce_hi,
+                                                 target, cap ? buf.data() : nullptr, cap, &r),
+              "bm_search_header_versions_hits_gpu");
+        buf.resize(static_cast<size_t>(r.stored));
+        hits = std::move(buf);
+        return r;
+    }
     // the double SHA-256 of the header under each nonce, 32 bytes each, most
     // significant byte first, on the first device: bm_header_hash_gpu
     std::vector<uint8_t> header_hash(const uint8_t header[80], const std::vector<uint32_t>& nonces) {

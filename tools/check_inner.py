@@ -19,7 +19,10 @@ from its header to its back edge is summed (the rare paths are laid out behind
 the back edge; one that was not would show as a memory op, its atomic).  The
 row gives VALU per nonce and per hash, the slow / fast split, the issue slots
 per hash under DESIGN.md section 5's model, max(slow, (slow + fast) / 2), and the
-v_readlane (SGPR spills read back), scratch and memory ops in that code."""
+v_readlane (SGPR spills read back), scratch and memory ops in that code.
+--header-versions-hits: check header_versions_hits_kernel<M> (the version-rolling
+share enumeration, the bm_header_versions_hits_inst unit), rows "hdrvh1",
+"hdrvh2", "hdrvh4", as --header-versions does."""
 import glob
 import os
 import re
@@ -39,7 +42,9 @@ rows = []
 HEADER = "--header" in sys.argv
 HEADER_HITS = "--header-hits" in sys.argv
 HEADER_VERSIONS = "--header-versions" in sys.argv
-for sfile in sorted(glob.glob(os.path.join(build, "*gfx950.s"))) if not (HEADER or HEADER_HITS or HEADER_VERSIONS) else []:
+HEADER_VERSIONS_HITS = "--header-versions-hits" in sys.argv
+HEADER_ANY = HEADER or HEADER_HITS or HEADER_VERSIONS or HEADER_VERSIONS_HITS
+for sfile in sorted(glob.glob(os.path.join(build, "*gfx950.s"))) if not HEADER_ANY else []:
     for name in isa_loops.kernels(sfile, "search_kernel"):
         m = re.search(r"search_kernel(_padc|_padk)?ILi(\d+)ELi(\d+)E(?:Li(\d+)E)?", name)
         if not m:
@@ -117,7 +122,7 @@ def loop_blocks(sfile, name):
             h = re.search(r"in Loop: Header=(BB\d+_\d+)", note)
             if h:
                 owner[cur] = ".L" + h.group(1)
-            elif "This Loop Header" in note:
+            elif "This Loop Header" in note or "This Inner Loop Header" in note:
                 owner[cur] = cur
         if m or note:
             continue
@@ -139,22 +144,25 @@ def loop_blocks(sfile, name):
 
 
 VROWS = []
-for sfile in sorted(glob.glob(os.path.join(build, "bm_header_versions_inst*gfx950.s"))) if HEADER_VERSIONS else []:
-    for name in isa_loops.kernels(sfile, "header_versions_kernel"):
-        slots = int(re.search(r"header_versions_kernelILi(\d+)E", name).group(1))
+VUNITS = ([("bm_header_versions_inst", "header_versions_kernel", "hdrv")] if HEADER_VERSIONS else []) + \
+         ([("bm_header_versions_hits_inst", "header_versions_hits_kernel", "hdrvh")] if HEADER_VERSIONS_HITS else [])
+for sfile, kernel, tag in [(f, k, t) for u, k, t in VUNITS
+                           for f in sorted(glob.glob(os.path.join(build, u + "*gfx950.s")))]:
+    for name in isa_loops.kernels(sfile, kernel):
+        slots = int(re.search(kernel + r"ILi(\d+)E", name).group(1))
         main = loop_blocks(sfile, name)
         body = [op for blk in main for op in blk]
         nbad = sum(1 for o, _ in body if BAD.match(o))
         nread = sum(1 for o, _ in body if o.startswith("v_readlane"))
         nlane = sum(1 for o, _ in body if LANE.match(o))
         fast, slow = classify(body)
-        rows.append((f"hdrv{slots}", 0, fast + slow, slow, nbad, nlane))
-        VROWS.append((slots, fast, slow, nbad, nread, nlane - nread,
+        rows.append((f"{tag}{slots}", 0, fast + slow, slow, nbad, nlane))
+        VROWS.append((tag, slots, fast, slow, nbad, nread, nlane - nread,
                       "+".join(str(sum(classify(blk))) for blk in main if sum(classify(blk)) >= 100)))
         bad += nbad > 0
-for slots, fast, slow, nbad, nread, nwrite, split in sorted(VROWS) if "-v" in sys.argv else []:
+for tag, slots, fast, slow, nbad, nread, nwrite, split in sorted(VROWS) if "-v" in sys.argv else []:
     valu = fast + slow
-    print(f" 0:hdrv{slots} inner VALU={valu} slow={slow} fast={fast} VALU/hash={valu / slots:.1f} "
+    print(f" 0:{tag}{slots} inner VALU={valu} slow={slow} fast={fast} VALU/hash={valu / slots:.1f} "
           f"slots/hash={max(slow, (slow + fast) / 2) / slots:.1f} mem={nbad} readlane={nread} writelane={nwrite} "
           f"blocks={split}")
 rows_printed = [r for r in rows if not r[0].startswith("hdrv") or r[4]]
