@@ -139,6 +139,11 @@ inline void header_hash_msb(const uint8_t header[kHeaderBytes], uint32_t nonce, 
     for (int i = 0; i < 32; ++i) hash[i] = d[31 - i];
 }
 
+// The top 64 bits of a hash in that order: what a device's partial or hit entry carries of it.
+inline uint64_t hash_top64(const uint8_t hash[32]) {
+    return ((uint64_t)load_be32(hash) << 32) | load_be32(hash + 4);
+}
+
 // The same double hash the way the kernel computes it, from a HeaderArgs:
 // rounds 3..63 of block 2 on the precomputed terms, then the second hash.
 // Only for checking header_precompute on the CPU.

@@ -37,9 +37,7 @@ inline int header_hits_collect(const uint8_t header[kHeaderBytes], const uint8_t
         h.nonce = (uint32_t)e.nonce;
         h.reserved = 0;
         if (std::memcmp(h.hash, target, 32) > 0) return BM_EINTERNAL;
-        uint64_t top = 0;
-        for (int k = 0; k < 8; ++k) top = (top << 8) | h.hash[k];
-        if (top != e.hash) return BM_EINTERNAL;
+        if (hash_top64(h.hash) != e.hash) return BM_EINTERNAL;
         out[i] = h;
     }
     return BM_OK;

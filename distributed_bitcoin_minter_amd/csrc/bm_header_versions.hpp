@@ -159,9 +159,7 @@ inline int header_versions_select(const uint8_t header[kHeaderBytes], const uint
     r.version = versions[vi];
     r.found = found ? 1 : 0;
     const bool meets = std::memcmp(r.hash, target, 32) <= 0;
-    uint64_t top = 0;
-    for (int i = 0; i < 8; ++i) top = (top << 8) | r.hash[i];
-    if (found ? !meets : (meets || top != best.hash)) return BM_EINTERNAL;
+    if (found ? !meets : (meets || hash_top64(r.hash) != best.hash)) return BM_EINTERNAL;
     *out = r;
     return BM_OK;
 }

@@ -48,9 +48,7 @@ inline int header_versions_hits_collect(const uint8_t header[kHeaderBytes], cons
         h.version = versions[vi];
         h.reserved = 0;
         if (std::memcmp(h.hash, target, 32) > 0) return BM_EINTERNAL;
-        uint64_t top = 0;
-        for (int k = 0; k < 8; ++k) top = (top << 8) | h.hash[k];
-        if (top != e.hash) return BM_EINTERNAL;
+        if (hash_top64(h.hash) != e.hash) return BM_EINTERNAL;
         out[i] = h;
     }
     return BM_OK;
@@ -70,9 +68,7 @@ inline int header_versions_hits_best(const uint8_t header[kHeaderBytes], const u
     uint8_t hash[32], hv[kHeaderBytes];
     header_with_version(header, versions[vi], hv);
     header_hash_msb(hv, key_nonce(best.nonce), hash);
-    uint64_t top = 0;
-    for (int i = 0; i < 8; ++i) top = (top << 8) | hash[i];
-    if (top != best.hash) return BM_EINTERNAL;
+    if (hash_top64(hash) != best.hash) return BM_EINTERNAL;
     if (count == 0 && std::memcmp(hash, target, 32) <= 0) return BM_EINTERNAL;
     std::memcpy(out->hash, hash, sizeof hash);
     out->nonce = key_nonce(best.nonce);

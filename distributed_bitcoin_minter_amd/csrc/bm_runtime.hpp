@@ -2,7 +2,7 @@
 // public interface is include/btcminer.h):
 //   bm_ctx.cpp     contexts and devices: lifetime, buffers, knobs, the rank join
 //   bm_combine.cpp the combine of a search's partials (RCCL allgather or host copies)
-//   bm_search.cpp  the six searches: kernel tables, sizing, enqueue, statistics
+//   bm_search.cpp  the seven searches: kernel tables, sizing, one call driver, statistics
 //   bm_aux.hip     the only unit with device code: the kernels of bm_aux_kernels.hpp,
 //                  a host wrapper that launches the reduction, and the entry points
 //                  built on them (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu)
@@ -124,8 +124,8 @@ struct Mode {
     bool every_hit() const {
         return kind == Kind::Hits || kind == Kind::HeaderHits || kind == Kind::HeaderVersionsHits;
     }
-    // a block-header call: one launch of HeaderArgs per device
-    bool header() const { return kind == Kind::Header || kind == Kind::HeaderHits; }
+    // the decimal modes whose kernels take the 64-bit target as a parameter
+    bool target64() const { return kind == Kind::Target || kind == Kind::Hits; }
 };
 
 // One kernel launch of a call, with what the ordering and the accounting of

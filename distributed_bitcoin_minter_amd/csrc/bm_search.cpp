@@ -1,10 +1,15 @@
 // bm_search.cpp -- the seven searches of include/btcminer.h (bm_search_gpu,
 // bm_search_target_gpu, bm_search_hits_gpu, bm_search_header_gpu,
 // bm_search_header_hits_gpu, bm_search_header_versions_gpu,
-// bm_search_header_versions_hits_gpu) over one path: plan and size every launch, enqueue each device's launches and its
-// second-pass reduction, combine the devices' partials, record the stats.
-// What differs between them is a Mode (bm_runtime.hpp) and the code around
-// that path in each *_impl.  Plain C++ over the HIP host API.
+// bm_search_header_versions_hits_gpu) over one path: plan and size every
+// launch, enqueue each device's launches and its second-pass reduction,
+// combine the devices' partials, read back what an enumeration appended,
+// record the stats.  run_call drives that path for the six searches outside a
+// rank group; what differs between them is a Mode (bm_runtime.hpp), the
+// planner each *_impl passes in (plan_decimal, plan_header, plan_versions, all
+// over plan_devices) and what it alone does with the outcome.  search_impl runs
+// the same stages around its group combine and the balance step.  Plain C++
+// over the HIP host API.
 //
 // bm_search_gpu is a drop-in for the reference miner's job loop body
 // (miner.go:58-65): the same (hash, nonce) for the same (msg, range).
@@ -122,9 +127,24 @@ int pad_fold_k(const bm_segment_t& s) {
     return (int)k;
 }
 
+// One device's launches as its planner sizes them (size_launch,
+// size_header_launch): each starts at the partial slot the one before it ended at.
+struct DevicePlan {
+    DeviceCtx& d;
+    const int di;
+    const Piece piece;  // never empty
+    std::vector<Launch>& list;
+    uint32_t off = 0;  // the next launch's first partial slot
+    void push(Launch& L) {
+        L.stat.device = di;
+        off += L.stat.grid;
+        list.push_back(L);
+    }
+};
+
 // The launch of one segment of a decimal search (Search, Target, Hits): tasks
 // of S = 10^ms nonces (ms <= digits of word LW), its grid by launch_geometry.
-int size_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const bm_segment_t& s, uint32_t part_off, Launch& L) {
+int size_launch(bm_ctx* ctx, DevicePlan& dp, Kind kind, const bm_segment_t& s) {
     // the folded kernel where it applies and this build registered it (an
     // A/B build may instantiate only some layouts): else the generic one,
     // which gives the same answer.  A target search and a hit enumeration
@@ -138,7 +158,7 @@ int size_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const bm_segment_t& s, uin
     // word LW holds one digit: the kernel steps the next one in word LW-1
     // (bm_kernels.hpp TWOW), so a task can still be 100 nonces
     if (s.p % 4 == 0 && s.p / 4 >= 1 && s.nd >= 2) ms = 2;
-    const uint64_t resident = resident_blocks(ctx, d, fn);
+    const uint64_t resident = resident_blocks(ctx, dp.d, fn);
     if (ctx->task_digits > 0) {
         ms = std::min(ms, ctx->task_digits);
     } else if (ms > 1) {
@@ -154,6 +174,7 @@ int size_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const bm_segment_t& s, uin
     const uint64_t t0 = s.vlo / S, t_end = s.vhi / S + 1;
     const LaunchGeometry g = launch_geometry(t_end - t0, S, ctx->lane_chunk, resident, kBlock);
 
+    Launch L;
     std::memset(&L, 0, sizeof L);
     SearchArgs& A = L.args.search;
     std::memcpy(A.mid, s.mid, sizeof A.mid);
@@ -173,7 +194,7 @@ int size_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const bm_segment_t& s, uin
     A.S = (uint32_t)S;
     A.ms = (uint32_t)ms;
     A.nd = (uint32_t)s.nd;
-    A.part_off = part_off;
+    A.part_off = dp.off;
     L.fn = fn;
     L.first_nonce = s.nonce_base + s.vlo;
     L.tasks = t_end - t0;
@@ -186,56 +207,47 @@ int size_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const bm_segment_t& s, uin
     L.stat.nonces = s.vhi - s.vlo + 1;
     L.stat.grid = g.grid;
     L.stat.tasks_per_thread = (uint32_t)g.tasks_per_thread;
+    dp.push(L);
     return BM_OK;
 }
 
-// One device's launch of header_kernel (Header) or header_hits_kernel
-// (HeaderHits): its piece [lo, hi] of the nonce range in tasks of 256 nonces.
-int size_header_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const HeaderArgs& base, uint32_t lo, uint32_t hi,
-                       Launch& L) {
-    const void* fn = kind == Kind::HeaderHits ? g_header_hits : g_header_search;
+// The kernel of a block-header mode that runs m versions in lock-step (m = 1
+// alone for Header and HeaderHits).
+const void* header_kernel_for(Kind kind, int m) {
+    switch (kind) {
+        case Kind::Header: return g_header_search;
+        case Kind::HeaderHits: return g_header_hits;
+        case Kind::HeaderVersions: return g_header_versions[m];
+        case Kind::HeaderVersionsHits: return g_header_versions_hits[m];
+        default: return nullptr;
+    }
+}
+
+HeaderArgs& args_of(Launch& L, const HeaderArgs&) { return L.args.header; }
+HeaderVersionsArgs<kMaxVersionSlots>& args_of(Launch& L, const HeaderVersionsArgs<kMaxVersionSlots>&) {
+    return L.args.versions;
+}
+
+// One device's launch of a block-header kernel: its piece of the nonce range in
+// tasks of 256 nonces, of m hashes each (base: the header's terms, or those of
+// one group of m versions).  Args: HeaderArgs or HeaderVersionsArgs.
+template <class Args>
+int size_header_launch(bm_ctx* ctx, DevicePlan& dp, Kind kind, const Args& base, int m) {
+    const void* fn = header_kernel_for(kind, m);
     if (!fn) return BM_EINTERNAL;
+    const uint32_t lo = (uint32_t)dp.piece.lo, hi = (uint32_t)dp.piece.hi;
+    Launch L;
     std::memset(&L, 0, sizeof L);
-    HeaderArgs& A = L.args.header;
+    Args& A = args_of(L, base);
     A = base;
     A.lo = lo;
     A.hi = hi;
     A.t0 = lo >> kHeaderTaskBits;
     A.ntask = (hi >> kHeaderTaskBits) - A.t0 + 1;
     const LaunchGeometry g = launch_geometry(A.ntask, kHeaderTaskNonces, ctx->lane_chunk,
-                                             resident_blocks(ctx, d, fn), kBlock);
+                                             resident_blocks(ctx, dp.d, fn), kBlock);
     A.chunk_m = g.chunk_m;
-    A.part_off = 0;
-    L.fn = fn;
-    L.first_nonce = lo;
-    L.tasks = A.ntask;
-    L.task_nonces = kHeaderTaskNonces;
-    L.stat.nbv = 1;
-    L.stat.nonces = (uint64_t)hi - lo + 1;
-    L.stat.grid = g.grid;
-    L.stat.tasks_per_thread = (uint32_t)g.tasks_per_thread;
-    return BM_OK;
-}
-
-// One device's launch of header_versions_kernel<m> (HeaderVersions) or
-// header_versions_hits_kernel<m> (HeaderVersionsHits): its piece [lo, hi] of the
-// nonce range for the m versions of one group (base holds their terms), in
-// tasks of 256 nonces of m hashes each.
-int size_versions_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const HeaderVersionsArgs<kMaxVersionSlots>& base,
-                         int m, uint32_t lo, uint32_t hi, uint32_t part_off, Launch& L) {
-    const void* fn = (kind == Kind::HeaderVersionsHits ? g_header_versions_hits : g_header_versions)[m];
-    if (!fn) return BM_EINTERNAL;
-    std::memset(&L, 0, sizeof L);
-    HeaderVersionsArgs<kMaxVersionSlots>& A = L.args.versions;
-    A = base;
-    A.lo = lo;
-    A.hi = hi;
-    A.t0 = lo >> kHeaderTaskBits;
-    A.ntask = (hi >> kHeaderTaskBits) - A.t0 + 1;
-    const LaunchGeometry g = launch_geometry(A.ntask, kHeaderTaskNonces, ctx->lane_chunk,
-                                             resident_blocks(ctx, d, fn), kBlock);
-    A.chunk_m = g.chunk_m;
-    A.part_off = part_off;
+    A.part_off = dp.off;
     L.fn = fn;
     L.first_nonce = lo;
     L.tasks = A.ntask;
@@ -244,6 +256,7 @@ int size_versions_launch(bm_ctx* ctx, DeviceCtx& d, Kind kind, const HeaderVersi
     L.stat.nonces = ((uint64_t)hi - lo + 1) * (uint64_t)m;
     L.stat.grid = g.grid;
     L.stat.tasks_per_thread = (uint32_t)g.tasks_per_thread;
+    dp.push(L);
     return BM_OK;
 }
 
@@ -278,18 +291,30 @@ int ensure_buffers(DeviceCtx& d, const Mode& mode, const std::vector<Launch>& la
     return grow(d, d.d_hbuf, d.hbuf_cap, std::max<size_t>(mode.cap, 1), sizeof(Partial), false, BM_ENOMEM);
 }
 
-// Stage 1 of a search: plan and size every launch of every device.  A decimal
-// search (msg, len): one launch per segment of the device's piece.  A header
-// search or enumeration (base): one launch per device.
-int plan_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* msg, size_t len, const HeaderArgs* base,
-                  uint64_t lower, uint64_t upper, std::vector<std::vector<Launch>>& launches) {
+// Stage 1 of every search: the range cut into the devices' pieces, and for each
+// device with a piece, with that device current, its launches as
+// per_device(DevicePlan&) sizes them and the room for what they write.
+template <class PerDevice>
+int plan_devices(bm_ctx* ctx, const Mode& mode, uint64_t lower, uint64_t upper,
+                 std::vector<std::vector<Launch>>& launches, PerDevice&& per_device) {
     const std::vector<Piece> pieces = plan_pieces(ctx, lower, upper);
     for (size_t di = 0; di < pieces.size(); ++di) {
         if (pieces[di].lo > pieces[di].hi) continue;
-        DeviceCtx& d = ctx->devs[di];
-        BM_HIP(hipSetDevice(d.id));
+        DevicePlan dp{ctx->devs[di], (int)di, pieces[di], launches[di]};
+        BM_HIP(hipSetDevice(dp.d.id));
+        BM_TRY(per_device(dp));
+        BM_TRY(ensure_buffers(dp.d, mode, launches[di]));
+    }
+    return BM_OK;
+}
+
+// A decimal search (Search, Target, Hits): one launch per segment of the
+// device's piece.
+int plan_decimal(bm_ctx* ctx, const Mode& mode, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                 std::vector<std::vector<Launch>>& launches) {
+    return plan_devices(ctx, mode, lower, upper, launches, [&](DevicePlan& dp) -> int {
         std::vector<bm_segment_t> segs;
-        if (!base) BM_TRY(plan_segments(msg, len, pieces[di].lo, pieces[di].hi, segs, ctx->max_windows));
+        BM_TRY(plan_segments(msg, len, dp.piece.lo, dp.piece.hi, segs, ctx->max_windows));
         // With streams to overlap on, the biggest segment's last tail_nonces
         // become a launch of their own: it is small enough for 10-nonce tasks
         // (size_launch), so the call ends on a short drain instead of half a
@@ -306,27 +331,28 @@ int plan_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* msg, size_t len,
                 segs.push_back(t);
             }
         }
-        uint32_t off = 0;
-        for (size_t i = 0; i < (base ? 1 : segs.size()); ++i) {
-            Launch L;
-            BM_TRY(base ? size_header_launch(ctx, d, mode.kind, *base, (uint32_t)pieces[di].lo,
-                                             (uint32_t)pieces[di].hi, L)
-                        : size_launch(ctx, d, mode.kind, segs[i], off, L));
-            L.stat.device = (int)di;
-            off += L.stat.grid;
-            launches[di].push_back(L);
-        }
-        BM_TRY(ensure_buffers(d, mode, launches[di]));
-    }
-    return BM_OK;
+        for (const bm_segment_t& seg : segs) BM_TRY(size_launch(ctx, dp, mode.kind, seg));
+        return BM_OK;
+    });
 }
 
-// Stage 1 of a version-rolling search or enumeration: every device gets one launch per group
-// of versions over its piece of the nonce range, in group order (they all
-// start at the piece's first nonce, so enqueue_device keeps that order).
-int plan_versions_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* header, const uint32_t* versions,
-                           size_t nver, const uint8_t* target, uint32_t lo, uint32_t hi,
-                           std::vector<std::vector<Launch>>& launches) {
+// A block-header search or enumeration (Header, HeaderHits): one launch per device.
+int plan_header(bm_ctx* ctx, const Mode& mode, const uint8_t* header, const uint8_t* target, uint32_t lo,
+                uint32_t hi, std::vector<std::vector<Launch>>& launches) {
+    HeaderArgs base;
+    std::memset(&base, 0, sizeof base);
+    host::header_precompute(header, base);
+    for (int i = 0; i < 8; ++i) base.tgt[i] = host::load_be32(target + 4 * i);
+    return plan_devices(ctx, mode, lo, hi, launches,
+                        [&](DevicePlan& dp) { return size_header_launch(ctx, dp, mode.kind, base, 1); });
+}
+
+// A version-rolling search or enumeration (HeaderVersions, HeaderVersionsHits):
+// every device gets one launch per group of versions over its piece of the
+// nonce range, in group order (they all start at the piece's first nonce, so
+// enqueue_device keeps that order).
+int plan_versions(bm_ctx* ctx, const Mode& mode, const uint8_t* header, const uint32_t* versions, size_t nver,
+                  const uint8_t* target, uint32_t lo, uint32_t hi, std::vector<std::vector<Launch>>& launches) {
     uint8_t sizes[BM_MAX_HEADER_VERSIONS];
     const int ngroups = host::versions_groups(nver, ctx->header_group, sizes);
     std::vector<HeaderVersionsArgs<kMaxVersionSlots>> groups((size_t)ngroups);
@@ -338,23 +364,11 @@ int plan_versions_launches(bm_ctx* ctx, const Mode& mode, const uint8_t* header,
         for (int i = 0; i < 8; ++i) groups[g].tgt[i] = host::load_be32(target + 4 * i);
         at += sizes[g];
     }
-    const std::vector<Piece> pieces = plan_pieces(ctx, lo, hi);
+    BM_TRY(plan_devices(ctx, mode, lo, hi, launches, [&](DevicePlan& dp) -> int {
+        for (int g = 0; g < ngroups; ++g) BM_TRY(size_header_launch(ctx, dp, mode.kind, groups[g], sizes[g]));
+        return BM_OK;
+    }));
     ctx->stats.nonces *= nver;  // pairs
-    for (size_t di = 0; di < pieces.size(); ++di) {
-        if (pieces[di].lo > pieces[di].hi) continue;
-        DeviceCtx& d = ctx->devs[di];
-        BM_HIP(hipSetDevice(d.id));
-        uint32_t off = 0;
-        for (int g = 0; g < ngroups; ++g) {
-            Launch L;
-            BM_TRY(size_versions_launch(ctx, d, mode.kind, groups[g], sizes[g], (uint32_t)pieces[di].lo,
-                                        (uint32_t)pieces[di].hi, off, L));
-            L.stat.device = (int)di;
-            off += L.stat.grid;
-            launches[di].push_back(L);
-        }
-        BM_TRY(ensure_buffers(d, mode, launches[di]));
-    }
     return BM_OK;
 }
 
@@ -420,16 +434,15 @@ int enqueue_device(bm_ctx* ctx, int di, const Mode& mode, std::vector<Launch>& l
         if (timed) BM_HIP(hipEventRecord(d.ev[2 * li], s));
         unsigned long long* ctr = d.d_ctr + kCtrStride * li;
         uint64_t target = mode.target, cap = mode.cap;
+        // the kernel's parameters: the launch's own, then what the mode adds
         void* params[7] = {&L.args, &d.d_part, &ctr};
-        auto more = [&](std::initializer_list<void*> v) { std::copy(v.begin(), v.end(), params + 3); };
-        switch (mode.kind) {
-            case Kind::Search: break;
-            case Kind::Target: more({&target, &d.d_hit}); break;
-            case Kind::Hits: more({&target, &d.d_hcount, &d.d_hbuf, &cap}); break;
-            case Kind::Header: more({&d.d_hit}); break;
-            case Kind::HeaderVersions: more({&d.d_hit}); break;
-            case Kind::HeaderHits: more({&d.d_hcount, &d.d_hbuf, &cap}); break;
-            case Kind::HeaderVersionsHits: more({&d.d_hcount, &d.d_hbuf, &cap}); break;
+        int np = 3;
+        if (mode.target64()) params[np++] = &target;
+        if (mode.first_hit()) params[np++] = &d.d_hit;
+        if (mode.every_hit()) {
+            params[np++] = &d.d_hcount;
+            params[np++] = &d.d_hbuf;
+            params[np++] = &cap;
         }
         BM_HIP(hipLaunchKernel(L.fn, dim3(L.stat.grid), dim3(kBlock), params, 0, s));
         if (timed) BM_HIP(hipEventRecord(d.ev[2 * li + 1], s));
@@ -594,6 +607,78 @@ uint64_t scan_hit_words(bm_ctx* ctx, const std::vector<std::vector<Launch>>& lau
     return hit;
 }
 
+// What the shared path of a call hands back to its *_impl.
+struct Call {
+    bool empty = false;                         // the range was: nothing ran, the impl's empty-range answer stands
+    std::vector<std::vector<Launch>> launches;  // per device
+    std::vector<uint32_t> first;                // per device: the launch that went out first
+    Partial best{UINT64_MAX, UINT64_MAX};       // the minimum of the devices' partials
+    // an every_hit mode: what the devices counted, and their entries (device 0's
+    // counts[0], then device 1's counts[1], ...) when there are any and they fit in cap
+    uint64_t count = 0;
+    std::vector<size_t> counts;
+    std::vector<Partial> entries;
+};
+
+// Stage 4 of an enumeration, after the combine has waited for every device's
+// copies: the counters, and the entries only when their sum fits in cap.
+// max_per_nonce: what one nonce of a device's piece can add to its counter at
+// most (an entry counts once); 0: no such bound.
+int read_back_hits(bm_ctx* ctx, const Mode& mode, uint64_t max_per_nonce, Call& c) {
+    const int ndev = (int)ctx->devs.size();
+    c.counts.assign(ndev, 0);
+    for (int di = 0; di < ndev; ++di) {
+        if (c.launches[di].empty()) continue;
+        const uint64_t n = *ctx->devs[di].h_hcount;
+        if (max_per_nonce && n > ctx->devs[di].piece_nonces * max_per_nonce) return BM_EINTERNAL;
+        c.counts[di] = (size_t)n;
+        c.count += n;
+    }
+    if (c.count > mode.cap || c.count == 0) return BM_OK;
+    c.entries.resize((size_t)c.count);
+    size_t at = 0;
+    for (int di = 0; di < ndev; ++di) {
+        DeviceCtx& d = ctx->devs[di];
+        if (c.counts[di] == 0) continue;
+        BM_HIP(hipSetDevice(d.id));
+        BM_HIP(hipMemcpyAsync(c.entries.data() + at, d.d_hbuf, c.counts[di] * sizeof(Partial), hipMemcpyDeviceToHost,
+                              d.stream));
+        BM_HIP(hipStreamSynchronize(d.stream));
+        at += c.counts[di];
+    }
+    return BM_OK;
+}
+
+// A call outside a rank group, start to end: the last call's stats go
+// (begin_call), plan(launches) plans and sizes every launch, enqueue, the host
+// combine (which also waits for every device's copies), an enumeration's
+// read-back and settle(), the stats.  settle is what an enumeration does with
+// its entries (sort, rehash, check): bm_stats_t.wall_ms has always covered
+// that, while a first-hit call's one rehash comes after the stats, in its
+// *_impl.  Any failure ends in fail_call.
+template <class Plan, class Settle>
+int run_call(bm_ctx* ctx, const Mode& mode, bool empty, Call& c, Plan&& plan, uint64_t max_per_nonce,
+             Settle&& settle) {
+    const auto t_start = std::chrono::steady_clock::now();
+    begin_call(ctx, mode);
+    c.empty = empty;
+    if (empty) return BM_OK;
+    const int ndev = (int)ctx->devs.size();
+    c.launches.resize(ndev);
+    c.first.assign(ndev, 0);
+    int rc = guarded([&] { return plan(c.launches); });
+    if (rc == BM_OK) rc = enqueue(ctx, mode, c.launches, c.first);
+    if (rc == BM_OK) rc = combine_local(ctx, &c.best, true);
+    if (rc == BM_OK && mode.every_hit()) rc = guarded([&] { return read_back_hits(ctx, mode, max_per_nonce, c); });
+    if (rc == BM_OK) rc = guarded([&] { return settle(); });
+    if (rc == BM_OK) rc = record_stats(ctx, c.launches, c.first, start_offsets(ctx), t_start);
+    return rc == BM_OK ? BM_OK : fail_call(ctx, rc);
+}
+template <class Plan>
+int run_call(bm_ctx* ctx, const Mode& mode, bool empty, Call& c, Plan&& plan) {  // a first-hit call
+    return run_call(ctx, mode, empty, c, plan, 0, [] { return BM_OK; });
+}
+
 int search_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, bm_result_t* out) {
     const auto t_start = std::chrono::steady_clock::now();
     const Mode mode{Kind::Search};
@@ -613,7 +698,7 @@ int search_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uin
     // so the context stays usable.
     std::vector<std::vector<Launch>> launches(ndev);
     std::vector<uint32_t> first(ndev, 0);
-    int rc = guarded([&] { return plan_launches(ctx, mode, msg, len, nullptr, lower, upper, launches); });
+    int rc = guarded([&] { return plan_decimal(ctx, mode, msg, len, lower, upper, launches); });
     if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
     if (rc != BM_OK) drain(ctx);
 
@@ -693,25 +778,15 @@ uint64_t host_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // lexicographic min of the partials when there is none.
 int target_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
                 bm_target_result_t* out) {
-    const auto t_start = std::chrono::steady_clock::now();
     const Mode mode{Kind::Target, target};
-    begin_call(ctx, mode);
-    const int ndev = (int)ctx->devs.size();
-    if (lower > upper) {
-        *out = bm_target_result_t{UINT64_MAX, UINT64_MAX, 0, 0};
-        return BM_OK;
-    }
+    *out = bm_target_result_t{UINT64_MAX, UINT64_MAX, 0, 0};
+    Call c;
+    const int rc = run_call(ctx, mode, lower > upper, c, [&](auto& launches) {
+        return plan_decimal(ctx, mode, msg, len, lower, upper, launches);
+    });
+    if (rc != BM_OK || c.empty) return rc;
 
-    std::vector<std::vector<Launch>> launches(ndev);
-    std::vector<uint32_t> first(ndev, 0);
-    Partial best{UINT64_MAX, UINT64_MAX};
-    int rc = guarded([&] { return plan_launches(ctx, mode, msg, len, nullptr, lower, upper, launches); });
-    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
-    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
-    if (rc == BM_OK) rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
-    if (rc != BM_OK) return fail_call(ctx, rc);
-
-    uint64_t hit = scan_hit_words(ctx, launches);
+    uint64_t hit = scan_hit_words(ctx, c.launches);
     bool found = hit != UINT64_MAX;
     // the nonce 2^64-1 cannot be told from "none" in the hit word: it is the
     // answer exactly when nothing below it hit and its own hash meets the target
@@ -719,7 +794,7 @@ int target_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uin
     if (found)
         *out = bm_target_result_t{host_hash(msg, len, hit), hit, 1, 0};
     else
-        *out = bm_target_result_t{best.hash, best.nonce, 0, 0};
+        *out = bm_target_result_t{c.best.hash, c.best.nonce, 0, 0};
     return BM_OK;
 }
 
@@ -731,53 +806,25 @@ int target_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uin
 // written last, on success only.
 int hits_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
               bm_result_t* hits, size_t cap, bm_hits_result_t* out) {
-    const auto t_start = std::chrono::steady_clock::now();
     const Mode mode{Kind::Hits, target, (uint64_t)cap};
-    begin_call(ctx, mode);
-    const int ndev = (int)ctx->devs.size();
-    if (lower > upper) {
-        *out = bm_hits_result_t{UINT64_MAX, UINT64_MAX, 0, 0};
+    *out = bm_hits_result_t{UINT64_MAX, UINT64_MAX, 0, 0};
+    Call c;
+    const int rc = run_call(ctx, mode, lower > upper, c, [&](auto& launches) {
+        return plan_decimal(ctx, mode, msg, len, lower, upper, launches);
+    }, 0 /* no bound on a device's count */, [&] {
+        auto at = c.entries.begin();
+        for (size_t n : c.counts) {
+            if (c.entries.empty()) break;  // none, or more than cap
+            std::sort(at, at + n, [](const Partial& a, const Partial& b) { return a.nonce < b.nonce; });
+            at += n;
+        }
         return BM_OK;
-    }
+    });
+    if (rc != BM_OK || c.empty) return rc;
 
-    std::vector<std::vector<Launch>> launches(ndev);
-    std::vector<uint32_t> first(ndev, 0);
-    std::vector<Partial> got;
-    Partial best{UINT64_MAX, UINT64_MAX};
-    uint64_t count = 0;
-    int rc = guarded([&] { return plan_launches(ctx, mode, msg, len, nullptr, lower, upper, launches); });
-    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
-    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
-    if (rc != BM_OK) return fail_call(ctx, rc);
-
-    for (int di = 0; di < ndev; ++di)
-        if (!launches[di].empty()) count += *ctx->devs[di].h_hcount;
-    if (count <= cap && count > 0) {
-        rc = guarded([&] {
-            got.resize((size_t)count);
-            size_t at = 0;
-            for (int di = 0; di < ndev; ++di) {
-                DeviceCtx& d = ctx->devs[di];
-                const size_t n = launches[di].empty() ? 0 : (size_t)*d.h_hcount;
-                if (n == 0) continue;
-                BM_HIP(hipSetDevice(d.id));
-                BM_HIP(hipMemcpyAsync(got.data() + at, d.d_hbuf, n * sizeof(Partial), hipMemcpyDeviceToHost, d.stream));
-                BM_HIP(hipStreamSynchronize(d.stream));
-                std::sort(got.begin() + at, got.begin() + at + n,
-                          [](const Partial& a, const Partial& b) { return a.nonce < b.nonce; });
-                at += n;
-            }
-            return (int)BM_OK;
-        });
-        if (rc != BM_OK) return fail_call(ctx, rc);
-    }
-    rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
-    if (rc != BM_OK) return fail_call(ctx, rc);
-
-    const uint64_t stored = count <= cap ? count : 0;
     static_assert(sizeof(bm_result_t) == sizeof(Partial), "hit entry layout");
-    if (stored) std::memcpy(hits, got.data(), (size_t)stored * sizeof(Partial));
-    *out = bm_hits_result_t{best.hash, best.nonce, count, stored};
+    if (!c.entries.empty()) std::memcpy(hits, c.entries.data(), c.entries.size() * sizeof(Partial));
+    *out = bm_hits_result_t{c.best.hash, c.best.nonce, c.count, c.entries.size()};
     return BM_OK;
 }
 
@@ -787,34 +834,19 @@ int hits_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint6
 // partials, and recomputes the full 256-bit hash of the one nonce it returns.
 int header_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, const uint8_t* target,
                 bm_header_result_t* out) {
-    const auto t_start = std::chrono::steady_clock::now();
     const Mode mode{Kind::Header};
-    begin_call(ctx, mode);
-    const int ndev = (int)ctx->devs.size();
-    if (lo > hi) {
-        std::memset(out->hash, 0xFF, sizeof out->hash);
-        out->nonce = 0xFFFFFFFFu;
-        out->found = 0;
-        return BM_OK;
-    }
+    std::memset(out->hash, 0xFF, sizeof out->hash);
+    out->nonce = 0xFFFFFFFFu;
+    out->found = 0;
+    Call c;
+    const int rc = run_call(ctx, mode, lo > hi, c, [&](auto& launches) {
+        return plan_header(ctx, mode, header, target, lo, hi, launches);
+    });
+    if (rc != BM_OK || c.empty) return rc;
 
-    HeaderArgs base;
-    std::memset(&base, 0, sizeof base);
-    host::header_precompute(header, base);
-    for (int i = 0; i < 8; ++i) base.tgt[i] = host::load_be32(target + 4 * i);
-
-    std::vector<std::vector<Launch>> launches(ndev);
-    std::vector<uint32_t> first(ndev, 0);
-    Partial best{UINT64_MAX, UINT64_MAX};
-    int rc = guarded([&] { return plan_launches(ctx, mode, nullptr, 0, &base, lo, hi, launches); });
-    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
-    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
-    if (rc == BM_OK) rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
-    if (rc != BM_OK) return fail_call(ctx, rc);
-
-    const uint64_t hit = scan_hit_words(ctx, launches);
+    const uint64_t hit = scan_hit_words(ctx, c.launches);
     const bool found = hit != UINT64_MAX;
-    const uint64_t n = found ? hit : best.nonce;
+    const uint64_t n = found ? hit : c.best.nonce;
     if (n > 0xFFFFFFFFull) return fail_call(ctx, BM_EINTERNAL);  // a non-empty range always has a minimum
     bm_header_result_t r;
     host::header_hash_msb(header, (uint32_t)n, r.hash);
@@ -822,9 +854,7 @@ int header_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, co
     r.found = found ? 1 : 0;
     // the device's claim against the host's hash of that nonce
     const bool meets = std::memcmp(r.hash, target, 32) <= 0;
-    uint64_t top = 0;
-    for (int i = 0; i < 8; ++i) top = (top << 8) | r.hash[i];
-    if (found ? !meets : (meets || top != best.hash)) return fail_call(ctx, BM_EINTERNAL);
+    if (found ? !meets : (meets || host::hash_top64(r.hash) != c.best.hash)) return fail_call(ctx, BM_EINTERNAL);
     *out = r;
     return BM_OK;
 }
@@ -838,78 +868,35 @@ int header_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, co
 // are written last, on success only.
 int header_hits_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, const uint8_t* target,
                      bm_header_hit_t* hits, size_t cap, bm_header_hits_result_t* out) {
-    const auto t_start = std::chrono::steady_clock::now();
     const Mode mode{Kind::HeaderHits, 0, (uint64_t)cap};
-    begin_call(ctx, mode);
-    const int ndev = (int)ctx->devs.size();
     bm_header_hits_result_t r;
     std::memset(&r, 0, sizeof r);
-    if (lo > hi) {
-        std::memset(r.hash, 0xFF, sizeof r.hash);
-        r.nonce = 0xFFFFFFFFu;
-        *out = r;
-        return BM_OK;
-    }
-
-    HeaderArgs base;
-    std::memset(&base, 0, sizeof base);
-    host::header_precompute(header, base);
-    for (int i = 0; i < 8; ++i) base.tgt[i] = host::load_be32(target + 4 * i);
-
-    std::vector<std::vector<Launch>> launches(ndev);
-    std::vector<uint32_t> first(ndev, 0);
-    std::vector<Partial> got;
+    std::memset(r.hash, 0xFF, sizeof r.hash);
+    r.nonce = 0xFFFFFFFFu;
+    *out = r;
     std::vector<bm_header_hit_t> list;
-    Partial best{UINT64_MAX, UINT64_MAX};
-    int rc = guarded([&] { return plan_launches(ctx, mode, nullptr, 0, &base, lo, hi, launches); });
-    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
-    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
-    if (rc != BM_OK) return fail_call(ctx, rc);
+    Call c;
+    const int rc = run_call(ctx, mode, lo > hi, c, [&](auto& launches) {
+        return plan_header(ctx, mode, header, target, lo, hi, launches);
+    }, 1 /* a nonce counts once */, [&]() -> int {
+        list.resize(c.entries.size());
+        if (!list.empty())
+            BM_TRY(host::header_hits_collect(header, target, lo, hi, c.entries.data(), c.counts.data(),
+                                             (int)c.counts.size(), list.data()));
+        // the best share: the device's claim against the host's hash of that nonce
+        if (c.best.nonce > 0xFFFFFFFFull) return BM_EINTERNAL;  // a non-empty range always has a minimum
+        host::header_hash_msb(header, (uint32_t)c.best.nonce, r.hash);
+        r.nonce = (uint32_t)c.best.nonce;
+        if (host::hash_top64(r.hash) != c.best.hash) return BM_EINTERNAL;
+        // ... and against the count: a best share at or below the target is itself a hit
+        if (c.count == 0 && std::memcmp(r.hash, target, 32) <= 0) return BM_EINTERNAL;
+        return BM_OK;
+    });
+    if (rc != BM_OK || c.empty) return rc;
 
-    uint64_t count = 0;
-    std::vector<size_t> counts(ndev, 0);
-    for (int di = 0; di < ndev; ++di) {
-        if (launches[di].empty()) continue;
-        const uint64_t c = *ctx->devs[di].h_hcount;
-        if (c > ctx->devs[di].piece_nonces) return fail_call(ctx, BM_EINTERNAL);  // a nonce counts once
-        counts[di] = (size_t)c;
-        count += c;
-    }
-    if (count <= cap && count > 0) {
-        rc = guarded([&] {
-            got.resize((size_t)count);
-            list.resize((size_t)count);
-            size_t at = 0;
-            for (int di = 0; di < ndev; ++di) {
-                DeviceCtx& d = ctx->devs[di];
-                if (counts[di] == 0) continue;
-                BM_HIP(hipSetDevice(d.id));
-                BM_HIP(hipMemcpyAsync(got.data() + at, d.d_hbuf, counts[di] * sizeof(Partial), hipMemcpyDeviceToHost,
-                                      d.stream));
-                BM_HIP(hipStreamSynchronize(d.stream));
-                at += counts[di];
-            }
-            return host::header_hits_collect(header, target, lo, hi, got.data(), counts.data(), ndev, list.data());
-        });
-        if (rc != BM_OK) return fail_call(ctx, rc);
-    }
-
-    // the best share: the device's claim against the host's hash of that nonce
-    if (best.nonce > 0xFFFFFFFFull) return fail_call(ctx, BM_EINTERNAL);  // a non-empty range always has a minimum
-    host::header_hash_msb(header, (uint32_t)best.nonce, r.hash);
-    r.nonce = (uint32_t)best.nonce;
-    uint64_t top = 0;
-    for (int i = 0; i < 8; ++i) top = (top << 8) | r.hash[i];
-    if (top != best.hash) return fail_call(ctx, BM_EINTERNAL);
-    // ... and against the count: a best share at or below the target is itself a hit
-    if (count == 0 && std::memcmp(r.hash, target, 32) <= 0) return fail_call(ctx, BM_EINTERNAL);
-
-    rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
-    if (rc != BM_OK) return fail_call(ctx, rc);
-
-    r.count = count;
-    r.stored = count <= cap ? count : 0;
-    if (r.stored) std::memcpy(hits, list.data(), (size_t)r.stored * sizeof(bm_header_hit_t));
+    r.count = c.count;
+    r.stored = list.size();
+    if (r.stored) std::memcpy(hits, list.data(), list.size() * sizeof(bm_header_hit_t));
     *out = r;
     return BM_OK;
 }
@@ -922,31 +909,20 @@ int header_hits_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t h
 // it (header_versions_select).
 int header_versions_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* versions, size_t nver, uint32_t lo,
                          uint32_t hi, const uint8_t* target, bm_header_versions_result_t* out) {
-    const auto t_start = std::chrono::steady_clock::now();
     const Mode mode{Kind::HeaderVersions};
-    begin_call(ctx, mode);
-    const int ndev = (int)ctx->devs.size();
-    if (lo > hi) {
-        std::memset(out, 0, sizeof *out);
-        std::memset(out->hash, 0xFF, sizeof out->hash);
-        out->nonce = 0xFFFFFFFFu;
-        out->version = versions[0];
-        return BM_OK;
-    }
+    std::memset(out, 0, sizeof *out);
+    std::memset(out->hash, 0xFF, sizeof out->hash);
+    out->nonce = 0xFFFFFFFFu;
+    out->version = versions[0];
+    Call c;
+    int rc = run_call(ctx, mode, lo > hi, c, [&](auto& launches) {
+        return plan_versions(ctx, mode, header, versions, nver, target, lo, hi, launches);
+    });
+    if (rc != BM_OK || c.empty) return rc;
 
-    std::vector<std::vector<Launch>> launches(ndev);
-    std::vector<uint32_t> first(ndev, 0);
-    Partial best{UINT64_MAX, UINT64_MAX};
-    int rc = guarded(
-        [&] { return plan_versions_launches(ctx, mode, header, versions, nver, target, lo, hi, launches); });
-    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
-    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
-    if (rc == BM_OK) rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
-    if (rc != BM_OK) return fail_call(ctx, rc);
-
-    const uint64_t hit = scan_hit_words(ctx, launches);
+    const uint64_t hit = scan_hit_words(ctx, c.launches);
     bm_header_versions_result_t r;
-    rc = host::header_versions_select(header, versions, nver, target, hit, best, &r);
+    rc = host::header_versions_select(header, versions, nver, target, hit, c.best, &r);
     if (rc != BM_OK) return fail_call(ctx, rc);
     *out = r;
     return BM_OK;
@@ -964,72 +940,44 @@ int header_versions_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* ver
 int header_versions_hits_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* versions, size_t nver,
                               uint32_t lo, uint32_t hi, const uint8_t* target, bm_header_version_hit_t* hits,
                               size_t cap, bm_header_versions_hits_result_t* out) {
-    const auto t_start = std::chrono::steady_clock::now();
     const Mode mode{Kind::HeaderVersionsHits, 0, (uint64_t)cap};
-    begin_call(ctx, mode);
-    const int ndev = (int)ctx->devs.size();
     bm_header_versions_hits_result_t r;
     std::memset(&r, 0, sizeof r);
-    if (lo > hi) {
-        std::memset(r.hash, 0xFF, sizeof r.hash);
-        r.nonce = 0xFFFFFFFFu;
-        r.version = versions[0];
-        *out = r;
-        return BM_OK;
-    }
-
-    std::vector<std::vector<Launch>> launches(ndev);
-    std::vector<uint32_t> first(ndev, 0);
-    std::vector<Partial> got;
+    std::memset(r.hash, 0xFF, sizeof r.hash);
+    r.nonce = 0xFFFFFFFFu;
+    r.version = versions[0];
+    *out = r;
     std::vector<bm_header_version_hit_t> list;
-    Partial best{UINT64_MAX, UINT64_MAX};
-    int rc = guarded(
-        [&] { return plan_versions_launches(ctx, mode, header, versions, nver, target, lo, hi, launches); });
-    if (rc == BM_OK) rc = enqueue(ctx, mode, launches, first);
-    if (rc == BM_OK) rc = combine_local(ctx, &best, true);  // also waits for every device's copies
-    if (rc != BM_OK) return fail_call(ctx, rc);
+    Call c;
+    const int rc = run_call(ctx, mode, lo > hi, c, [&](auto& launches) {
+        return plan_versions(ctx, mode, header, versions, nver, target, lo, hi, launches);
+    }, nver /* a pair counts once */, [&]() -> int {
+        list.resize(c.entries.size());
+        if (!list.empty())
+            BM_TRY(host::header_versions_hits_collect(header, versions, nver, target, lo, hi, c.entries.data(),
+                                                      c.counts.data(), (int)c.counts.size(), list.data()));
+        // the best share: the device's claim against the host's hash of that pair, and against the count
+        return host::header_versions_hits_best(header, versions, nver, target, c.best, c.count, &r);
+    });
+    if (rc != BM_OK || c.empty) return rc;
 
-    uint64_t count = 0;
-    std::vector<size_t> counts(ndev, 0);
-    for (int di = 0; di < ndev; ++di) {
-        if (launches[di].empty()) continue;
-        const uint64_t c = *ctx->devs[di].h_hcount;
-        if (c > ctx->devs[di].piece_nonces * (uint64_t)nver) return fail_call(ctx, BM_EINTERNAL);  // a pair counts once
-        counts[di] = (size_t)c;
-        count += c;
-    }
-    if (count <= cap && count > 0) {
-        rc = guarded([&] {
-            got.resize((size_t)count);
-            list.resize((size_t)count);
-            size_t at = 0;
-            for (int di = 0; di < ndev; ++di) {
-                DeviceCtx& d = ctx->devs[di];
-                if (counts[di] == 0) continue;
-                BM_HIP(hipSetDevice(d.id));
-                BM_HIP(hipMemcpyAsync(got.data() + at, d.d_hbuf, counts[di] * sizeof(Partial), hipMemcpyDeviceToHost,
-                                      d.stream));
-                BM_HIP(hipStreamSynchronize(d.stream));
-                at += counts[di];
-            }
-            return host::header_versions_hits_collect(header, versions, nver, target, lo, hi, got.data(),
-                                                      counts.data(), ndev, list.data());
-        });
-        if (rc != BM_OK) return fail_call(ctx, rc);
-    }
-
-    // the best share: the device's claim against the host's hash of that pair, and against the count
-    rc = host::header_versions_hits_best(header, versions, nver, target, best, count, &r);
-    if (rc != BM_OK) return fail_call(ctx, rc);
-
-    rc = record_stats(ctx, launches, first, start_offsets(ctx), t_start);
-    if (rc != BM_OK) return fail_call(ctx, rc);
-
-    r.count = count;
-    r.stored = count <= cap ? count : 0;
-    if (r.stored) std::memcpy(hits, list.data(), (size_t)r.stored * sizeof(bm_header_version_hit_t));
+    r.count = c.count;
+    r.stored = list.size();
+    if (r.stored) std::memcpy(hits, list.data(), list.size() * sizeof(bm_header_version_hit_t));
     *out = r;
     return BM_OK;
+}
+
+// The tail of every bm_search_*_gpu once it has checked its arguments:
+// impl(&r) with the caller's current device kept and no exception leaving the
+// C ABI; *out is written on success only.
+template <class R, class Impl>
+int call_into(R* out, Impl&& impl) {
+    DeviceGuard guard;
+    R r;
+    const int rc = guarded([&] { return impl(&r); });
+    if (rc == BM_OK) *out = r;
+    return rc;
 }
 
 }  // namespace
@@ -1039,22 +987,16 @@ extern "C" {
 
 int bm_search_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, bm_result_t* out) {
     if (!ctx || !out || (len && !msg) || len > BM_MAX_MSG_LEN) return BM_EINVAL;
-    bm::DeviceGuard guard;
-    bm_result_t r;
-    int rc = bm::guarded([&] { return bm::search_impl(ctx, msg, len, lower, upper, &r); });
-    if (rc == BM_OK) *out = r;
-    return rc;
+    return bm::call_into(out, [&](bm_result_t* r) { return bm::search_impl(ctx, msg, len, lower, upper, r); });
 }
 
 int bm_search_target_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
                          uint64_t target, bm_target_result_t* out) {
     if (!ctx || !out || (len && !msg) || len > BM_MAX_MSG_LEN) return BM_EINVAL;
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // the group's allgather slot carries no hit
-    bm::DeviceGuard guard;
-    bm_target_result_t r;
-    int rc = bm::guarded([&] { return bm::target_impl(ctx, msg, len, lower, upper, target, &r); });
-    if (rc == BM_OK) *out = r;
-    return rc;
+    return bm::call_into(out, [&](bm_target_result_t* r) {
+        return bm::target_impl(ctx, msg, len, lower, upper, target, r);
+    });
 }
 
 int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
@@ -1062,22 +1004,18 @@ int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t l
     if (!ctx || !out || (len && !msg) || len > BM_MAX_MSG_LEN) return BM_EINVAL;
     if (cap > BM_MAX_HITS || (!hits && cap > 0)) return BM_EINVAL;
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // the group's allgather slot carries no hits
-    bm::DeviceGuard guard;
-    bm_hits_result_t r;
-    int rc = bm::guarded([&] { return bm::hits_impl(ctx, msg, len, lower, upper, target, hits, cap, &r); });
-    if (rc == BM_OK) *out = r;
-    return rc;
+    return bm::call_into(out, [&](bm_hits_result_t* r) {
+        return bm::hits_impl(ctx, msg, len, lower, upper, target, hits, cap, r);
+    });
 }
 
 int bm_search_header_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t nonce_lo, uint32_t nonce_hi,
                          const uint8_t* target, bm_header_result_t* out) {
     if (!ctx || !header || !target || !out) return BM_EINVAL;
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
-    bm::DeviceGuard guard;
-    bm_header_result_t r;
-    int rc = bm::guarded([&] { return bm::header_impl(ctx, header, nonce_lo, nonce_hi, target, &r); });
-    if (rc == BM_OK) *out = r;
-    return rc;
+    return bm::call_into(out, [&](bm_header_result_t* r) {
+        return bm::header_impl(ctx, header, nonce_lo, nonce_hi, target, r);
+    });
 }
 
 int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t nonce_lo, uint32_t nonce_hi,
@@ -1086,12 +1024,9 @@ int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t non
     if (!ctx || !header || !target || !out) return BM_EINVAL;
     if (cap > BM_MAX_HEADER_HITS || (!hits && cap > 0)) return BM_EINVAL;
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
-    bm::DeviceGuard guard;
-    bm_header_hits_result_t r;
-    int rc = bm::guarded(
-        [&] { return bm::header_hits_impl(ctx, header, nonce_lo, nonce_hi, target, hits, cap, &r); });
-    if (rc == BM_OK) *out = r;
-    return rc;
+    return bm::call_into(out, [&](bm_header_hits_result_t* r) {
+        return bm::header_hits_impl(ctx, header, nonce_lo, nonce_hi, target, hits, cap, r);
+    });
 }
 
 int bm_search_header_versions_gpu(bm_ctx_t* ctx, const uint8_t* header, const uint32_t* versions, size_t nver,
@@ -1100,13 +1035,9 @@ int bm_search_header_versions_gpu(bm_ctx_t* ctx, const uint8_t* header, const ui
     if (!ctx || !header || !versions || !target || !out) return BM_EINVAL;
     if (nver == 0 || nver > BM_MAX_HEADER_VERSIONS) return BM_EINVAL;
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
-    bm::DeviceGuard guard;
-    bm_header_versions_result_t r;
-    int rc = bm::guarded([&] {
-        return bm::header_versions_impl(ctx, header, versions, nver, nonce_lo, nonce_hi, target, &r);
+    return bm::call_into(out, [&](bm_header_versions_result_t* r) {
+        return bm::header_versions_impl(ctx, header, versions, nver, nonce_lo, nonce_hi, target, r);
     });
-    if (rc == BM_OK) *out = r;
-    return rc;
 }
 
 int bm_search_header_versions_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, const uint32_t* versions, size_t nver,
@@ -1117,13 +1048,9 @@ int bm_search_header_versions_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, con
     if (nver == 0 || nver > BM_MAX_HEADER_VERSIONS) return BM_EINVAL;
     if (cap > BM_MAX_HEADER_HITS || (!hits && cap > 0)) return BM_EINVAL;
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
-    bm::DeviceGuard guard;
-    bm_header_versions_hits_result_t r;
-    int rc = bm::guarded([&] {
-        return bm::header_versions_hits_impl(ctx, header, versions, nver, nonce_lo, nonce_hi, target, hits, cap, &r);
+    return bm::call_into(out, [&](bm_header_versions_hits_result_t* r) {
+        return bm::header_versions_hits_impl(ctx, header, versions, nver, nonce_lo, nonce_hi, target, hits, cap, r);
     });
-    if (rc == BM_OK) *out = r;
-    return rc;
 }
 
 int bm_header_target_from_bits(uint32_t nbits, uint8_t* target) {

@@ -33,8 +33,13 @@ T_SOME = (1 << 64) >> 12  # about 256 of 2^20 nonces meet it
 T_FEW = (1 << 64) >> 16   # about 16 of 2^20
 H_SOME = (1 << 244) - 1   # about 1 nonce in 2^12 meets it
 HDR3 = dict(devices=[0, 0, 0], lo=393216, hi=393216 + 3 * 2**15 - 1)
+ONE_NONCE3 = dict(devices=[0, 0, 0], lo=8603, hi=8603)  # one nonce and two empty pieces
+R18 = dict(lo=0, hi=2**18 - 1)
+# seven versions (groups 4 + 2 + 1), one of them twice: tools/header_versions_hits_check.cpp's
+VERSIONS7 = [0x20000000, 0x20002000, 1, 0x3FFFE000, 0, 0x20002000, 0xFFFFFFFF]
 
-# name -> the call.  kind: search | target | hits | header; knobs are Context setters.
+# name -> the call.  kind: search | target | hits | header | header_hits | header_versions |
+# header_versions_hits; knobs are Context setters.
 CASES = [
     dict(name="search_digit_boundaries", kind="search", msg=b"msg".hex(), lo=0, hi=99999),
     dict(name="search_tail_split_bpc1", kind="search", blocks_per_cu=1, **BRADFITZ),
@@ -55,6 +60,22 @@ CASES = [
     dict(name="header_three_found", kind="header", target=H_SOME, **HDR3),
     dict(name="header_three_none", kind="header", target=0, **HDR3),
     dict(name="header_one_nonce_two_empty", kind="header", devices=[0, 0, 0], lo=8603, hi=8603, target=0),
+    dict(name="header_hits_one_device", kind="header_hits", lo=0, hi=2**20 - 1, target=H_SOME, cap=4096),
+    dict(name="header_hits_three", kind="header_hits", target=H_SOME, cap=4096, **HDR3),
+    dict(name="header_hits_three_overflow", kind="header_hits", target=H_SOME, cap=1, **HDR3),
+    dict(name="header_hits_one_nonce_two_empty", kind="header_hits", target=H_SOME, cap=4096, **ONE_NONCE3),
+    dict(name="header_versions_one_device_none", kind="header_versions", versions=VERSIONS7, target=0, **R18),
+    dict(name="header_versions_three_none", kind="header_versions", versions=VERSIONS7, target=0, **HDR3),
+    dict(name="header_versions_three_found", kind="header_versions", versions=VERSIONS7, target=H_SOME, **HDR3),
+    dict(name="header_versions_one_version", kind="header_versions", versions=VERSIONS7[:1], target=0, **R18),
+    dict(name="header_versions_hits_one_device", kind="header_versions_hits", versions=VERSIONS7, target=H_SOME,
+         cap=4096, **R18),
+    dict(name="header_versions_hits_three", kind="header_versions_hits", versions=VERSIONS7, target=H_SOME, cap=4096,
+         **HDR3),
+    dict(name="header_versions_hits_three_overflow", kind="header_versions_hits", versions=VERSIONS7, target=H_SOME,
+         cap=1, **HDR3),
+    dict(name="header_versions_hits_one_nonce_two_empty", kind="header_versions_hits", versions=VERSIONS7,
+         target=H_SOME, cap=4096, **ONE_NONCE3),
 ]
 assert all(c["hi"] - c["lo"] < 2**28 for c in CASES)
 
@@ -82,9 +103,19 @@ def run_case(Context, case):
         elif case["kind"] == "hits":
             count, hits, best = ctx.search_hits(bytes.fromhex(case["msg"]), lo, hi, case["target"], case["cap"])
             result = [count, [list(x) for x in hits], list(best)]
-        else:
+        elif case["kind"] == "header":
             found, h, n = ctx.search_header(genesis_header(), lo, hi, case["target"])
             result = [found, str(h), n]  # a 256-bit integer: as a decimal string
+        elif case["kind"] == "header_hits":
+            count, hits, (h, n) = ctx.search_header_hits(genesis_header(), lo, hi, case["target"], case["cap"])
+            result = [count, None if hits is None else [[str(x), m] for x, m in hits], [str(h), n]]
+        elif case["kind"] == "header_versions":
+            found, h, n, i = ctx.search_header_versions(genesis_header(), case["versions"], lo, hi, case["target"])
+            result = [found, str(h), n, i]
+        else:
+            count, hits, (h, n, i) = ctx.search_header_versions_hits(genesis_header(), case["versions"], lo, hi,
+                                                                     case["target"], case["cap"])
+            result = [count, None if hits is None else [[str(x), m, k] for x, m, k in hits], [str(h), n, i]]
         st = ctx.last_stats()
         rec = dict(result=result, launches=st.launches, nonces=st.nonces,
                    launch=[[L.device, L.p, L.nbv, L.pad_block, L.digits, L.inner_digits, L.nonces, L.grid,
@@ -92,6 +123,29 @@ def run_case(Context, case):
         if found is False:  # a full scan: every task was handed out
             rec["nonces_dispatched"] = ctx.last_target_stats().nonces_dispatched
         return rec
+
+
+def cpu_hit_count(case):
+    """How many (nonce, version) pairs of a header enumeration's window meet its target, from hashlib."""
+    import hashlib
+    import struct
+    header = genesis_header()
+    heads = [struct.pack("<I", v) + header[4:76] for v in case.get("versions", [struct.unpack("<I", header[:4])[0]])]
+    return sum(int.from_bytes(hashlib.sha256(hashlib.sha256(head + struct.pack("<I", n)).digest()).digest(),
+                              "little") <= case["target"]
+               for n in range(case["lo"], case["hi"] + 1) for head in heads)
+
+
+def check_windows():
+    """Before recording: an H_SOME enumeration does contain hits (an overflow
+    case more than its cap), unless its window is the single nonce."""
+    counts = {}
+    for case in CASES:
+        if case["kind"] in ("header_hits", "header_versions_hits") and case["hi"] > case["lo"]:
+            counts[case["name"]] = n = cpu_hit_count(case)
+            assert n > (case["cap"] if case["cap"] < 4096 else 0), (case["name"], n)
+            assert case["cap"] < 4096 or n <= case["cap"], (case["name"], n)
+    return counts
 
 
 def device_cus(Context):
@@ -105,10 +159,13 @@ def main():
     ap.add_argument("--made-from", required=True, help="the commit whose build is loaded (BTCMINER_LIB)")
     args = ap.parse_args()
     from distributed_bitcoin_minter_amd import Context, _lib
+    counts = check_windows()
     doc = dict(made_from=args.made_from, library=os.path.basename(os.path.dirname(_lib.LIB_PATH)) + "/" +
                os.path.basename(_lib.LIB_PATH), cus=device_cus(Context), columns=[
                    "device", "p", "nbv", "pad_block", "digits", "inner_digits", "nonces", "grid", "tasks_per_thread"],
                cases=[dict(case, expect=run_case(Context, case)) for case in CASES])
+    for case in doc["cases"]:  # the enumerations' counts against hashlib's
+        assert case["name"] not in counts or case["expect"]["result"][0] == counts[case["name"]], case["name"]
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")

@@ -1,6 +1,6 @@
 """Launch geometry and per-call host behaviour, pinned.
 
-tests/golden/launch_shape.json holds, for a fixed table of calls (all four
+tests/golden/launch_shape.json holds, for a fixed table of calls (all seven
 searches; one device and three slots of one device), the result and every
 bm_launch_stat_t the library recorded: layout, task size, grid, tasks per
 thread.  It was recorded from the build of the commit named in its

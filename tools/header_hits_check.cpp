@@ -17,6 +17,8 @@
 
 namespace {
 
+using bm::host::hash_top64;
+
 int fails = 0;
 
 void expect(bool ok, const char* what) {
@@ -36,19 +38,13 @@ uint32_t rnd() {
     return rng_state >> 8;
 }
 
-uint64_t top64(const uint8_t hash[32]) {
-    uint64_t t = 0;
-    for (int k = 0; k < 8; ++k) t = (t << 8) | hash[k];
-    return t;
-}
-
 // Every hit of [lo, hi] at `target`, ascending: what the devices report.
 std::vector<bm::Partial> true_hits(const uint8_t* header, const uint8_t* target, uint32_t lo, uint32_t hi) {
     std::vector<bm::Partial> v;
     for (uint64_t n = lo; n <= hi; ++n) {
         uint8_t h[32];
         bm::host::header_hash_msb(header, (uint32_t)n, h);
-        if (std::memcmp(h, target, 32) <= 0) v.push_back(bm::Partial{top64(h), n});
+        if (std::memcmp(h, target, 32) <= 0) v.push_back(bm::Partial{hash_top64(h), n});
     }
     return v;
 }
@@ -129,14 +125,14 @@ int main() {
         bm::host::header_hash_msb(header, miss, h);
         if (std::memcmp(h, target, 32) > 0) break;
     }
-    const uint64_t miss_top = top64(h);
+    const uint64_t miss_top = hash_top64(h);
     uint32_t below = lo - 1, above = hi + 1;  // hits outside the range, if they were in it
     uint8_t ones[32];
     std::memset(ones, 0xFF, sizeof ones);
     bm::host::header_hash_msb(header, below, h);
-    const uint64_t below_top = top64(h);
+    const uint64_t below_top = hash_top64(h);
     bm::host::header_hash_msb(header, above, h);
-    const uint64_t above_top = top64(h);
+    const uint64_t above_top = hash_top64(h);
     const Forge forges[] = {
         {"a nonce whose hash is above the target", {miss_top, miss}, true},
         {"a wrong top 64 bits", {truth[5].hash ^ 1, truth[5].nonce}, true},

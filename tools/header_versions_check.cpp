@@ -23,6 +23,8 @@
 
 namespace {
 
+using bm::host::hash_top64;
+
 int fails = 0;
 
 void expect(bool ok, const char* what) {
@@ -44,12 +46,6 @@ const uint32_t kFirstNonce[2] = {2083236893u - 10000u, 0xFFFFFFFFu - 19999u};  /
 constexpr int kVersions = 5;
 const uint32_t kVersionList[kVersions] = {0u, 1u, 0x20000000u, 0x3fffe000u, 0xffffffffu};
 constexpr uint32_t kNoncesPerVersion = 20000;
-
-uint64_t top64(const uint8_t hash[32]) {
-    uint64_t t = 0;
-    for (int k = 0; k < 8; ++k) t = (t << 8) | hash[k];
-    return t;
-}
 
 template <int M>
 void check_group(const uint8_t* header, const uint32_t* versions, size_t first, int m, uint32_t n0,
@@ -175,7 +171,7 @@ int main() {
                 } else if (miss == UINT64_MAX) {
                     miss = key;
                 }
-                const uint64_t top = top64(hash);
+                const uint64_t top = hash_top64(hash);
                 if (top < best.hash || (top == best.hash && key < best.nonce)) best = bm::Partial{top, key};
             }
         expect(hit != UINT64_MAX, "the window holds a hit");
@@ -194,7 +190,7 @@ int main() {
         expect(bm::host::header_versions_select(header.get(), versions.get(), kVersions, zero, UINT64_MAX, best,
                                                 out.get()) == BM_OK &&
                    out->found == 0 && bm::host::versions_key(out->nonce, out->version_index) == best.nonce &&
-                   top64(out->hash) == best.hash && out->version == versions[out->version_index],
+                   hash_top64(out->hash) == best.hash && out->version == versions[out->version_index],
                "a true best share is returned");
 
         std::memset(out.get(), 0xA5, sizeof *out);

@@ -19,6 +19,8 @@
 
 namespace {
 
+using bm::host::hash_top64;
+
 int fails = 0;
 
 void expect(bool ok, const char* what) {
@@ -42,12 +44,6 @@ uint32_t rnd() {
     return rng_state >> 8;
 }
 
-uint64_t top64(const uint8_t hash[32]) {
-    uint64_t t = 0;
-    for (int k = 0; k < 8; ++k) t = (t << 8) | hash[k];
-    return t;
-}
-
 void pair_hash(const uint8_t* header, uint32_t vi, uint32_t nonce, uint8_t out[32]) {
     uint8_t hv[bm::kHeaderBytes];
     bm::host::header_with_version(header, kVersions[vi], hv);
@@ -61,7 +57,7 @@ std::vector<bm::Partial> true_hits(const uint8_t* header, const uint8_t* target,
         for (uint32_t i = 0; i < kNver; ++i) {
             uint8_t h[32];
             pair_hash(header, i, (uint32_t)n, h);
-            if (std::memcmp(h, target, 32) <= 0) v.push_back(bm::Partial{top64(h), bm::host::versions_key((uint32_t)n, i)});
+            if (std::memcmp(h, target, 32) <= 0) v.push_back(bm::Partial{hash_top64(h), bm::host::versions_key((uint32_t)n, i)});
         }
     return v;
 }
@@ -156,14 +152,14 @@ int main() {
         pair_hash(header, 0, miss, h);
         if (std::memcmp(h, target, 32) > 0) break;
     }
-    const uint64_t miss_top = top64(h);
+    const uint64_t miss_top = hash_top64(h);
     const uint32_t below = lo - 1, above = hi + 1;
     uint8_t ones[32];
     std::memset(ones, 0xFF, sizeof ones);
     pair_hash(header, 2, below, h);
-    const uint64_t below_top = top64(h);
+    const uint64_t below_top = hash_top64(h);
     pair_hash(header, 2, above, h);
-    const uint64_t above_top = top64(h);
+    const uint64_t above_top = hash_top64(h);
     // index 5 of a list cut to 5 versions: a true hash of the full list, but no index of this call
     size_t at5 = 0;
     while ((uint32_t)truth[at5].nonce != 5) ++at5;
@@ -173,7 +169,7 @@ int main() {
         {"a pair whose hash is above the target", {miss_top, bm::host::versions_key(miss, 0)}, true, false},
         {"a wrong top 64 bits", {truth[5].hash ^ 1, truth[5].nonce}, true, false},
         {"a wrong top 64 bits, high word", {truth[5].hash ^ (1ull << 63), truth[5].nonce}, true, false},
-        {"the top 64 bits of another version's hash", {top64(h), truth[5].nonce}, true, false},
+        {"the top 64 bits of another version's hash", {hash_top64(h), truth[5].nonce}, true, false},
         {"a nonce below the range", {below_top, bm::host::versions_key(below, 2)}, false, true},
         {"a nonce above the range", {above_top, bm::host::versions_key(above, 2)}, false, true},
         {"an index at nver", {truth[5].hash, bm::host::versions_key(n5, (uint32_t)kNver)}, true, false},
@@ -216,7 +212,7 @@ int main() {
         for (uint32_t n = lo; n <= hi; ++n)
             for (uint32_t i = 0; i < kNver; ++i) {
                 pair_hash(header, i, n, h);
-                const bm::Partial p{top64(h), bm::host::versions_key(n, i)};
+                const bm::Partial p{hash_top64(h), bm::host::versions_key(n, i)};
                 if (p.hash < best.hash || (p.hash == best.hash && p.nonce < best.nonce)) best = p;
             }
         bm_header_versions_hits_result_t r;
