@@ -11,10 +11,11 @@ re-built as gfx950 HIP kernels behind the C ABI in include/btcminer.h
 """
 from . import bitcoin, dist
 from ._lib import (BtcMinerError, Context, HeaderHit, HeaderHitsResult, HeaderVersionHit, HeaderVersionsHitsResult,
-                   HeaderVersionsResult, HitsResult, LIB_PATH, bits_to_target, device_count, plan_segments,
-                   rccl_unique_id, roll_versions)
+                   HeaderVersionsResult, HitsResult, Job, JobShare, JobSharesResult, LIB_PATH, bits_to_target,
+                   device_count, difficulty_to_target, plan_segments, rccl_unique_id, roll_versions, submit_params)
 from .miner import Miner
 
 __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", "HeaderHitsResult",
-           "HeaderVersionHit", "HeaderVersionsHitsResult", "HeaderVersionsResult", "HitsResult", "LIB_PATH",
-           "bits_to_target", "device_count", "plan_segments", "rccl_unique_id", "roll_versions"]
+           "HeaderVersionHit", "HeaderVersionsHitsResult", "HeaderVersionsResult", "HitsResult", "Job", "JobShare",
+           "JobSharesResult", "LIB_PATH", "bits_to_target", "device_count", "difficulty_to_target", "plan_segments", "rccl_unique_id",
+           "roll_versions", "submit_params"]

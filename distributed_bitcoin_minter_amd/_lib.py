@@ -116,6 +116,32 @@ class HeaderVersionsHitsResult(ctypes.Structure):
                 ("reserved", c_u32), ("count", c_u64), ("stored", c_u64)]
 
 
+BM_MAX_JOB_COINBASE = 1 << 16
+BM_MAX_JOB_BRANCH = 32
+BM_MAX_JOB_HEADERS = 4096
+DIFF1_TARGET = 0xffff << 208  # the target of difficulty 1 (nbits 1d00ffff)
+
+
+class JobStruct(ctypes.Structure):
+    """bm_job_t: the pointers are borrowed (Job keeps the buffers alive)."""
+    _fields_ = [("coinb1", ctypes.c_char_p), ("coinb1_len", ctypes.c_size_t),
+                ("extranonce1", ctypes.c_char_p), ("extranonce1_len", ctypes.c_size_t),
+                ("extranonce2_size", c_u32),
+                ("coinb2", ctypes.c_char_p), ("coinb2_len", ctypes.c_size_t),
+                ("branch", ctypes.c_char_p), ("nbranch", ctypes.c_size_t),
+                ("prevhash", ctypes.c_uint8 * 32), ("version", c_u32), ("nbits", c_u32)]
+
+
+class JobShare(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("extranonce2", c_u64), ("nonce", c_u32), ("ntime", c_u32),
+                ("version_index", c_u32), ("version", c_u32), ("is_block", c_u32), ("reserved", c_u32)]
+
+
+class JobSharesResult(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("extranonce2", c_u64), ("nonce", c_u32), ("version_index", c_u32),
+                ("version", c_u32), ("reserved", c_u32), ("count", c_u64), ("stored", c_u64), ("headers", c_u64)]
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -200,6 +226,12 @@ def _open(path):
                                                 P(HeaderVersionsHitsResult)], ctypes.c_int),
         "bm_header_hash_gpu": ([vp, ctypes.c_char_p, P(c_u32), ctypes.c_size_t, P(ctypes.c_uint8)], ctypes.c_int),
         "bm_header_target_from_bits": ([c_u32, P(ctypes.c_uint8)], ctypes.c_int),
+        "bm_job_prevhash_from_stratum": ([ctypes.c_char_p, P(ctypes.c_uint8)], ctypes.c_int),
+        "bm_job_header": ([P(JobStruct), c_u64, c_u32, c_u32, P(ctypes.c_uint8)], ctypes.c_int),
+        "bm_target_from_difficulty": ([ctypes.c_double, P(ctypes.c_uint8)], ctypes.c_int),
+        "bm_search_job_shares_gpu": ([vp, P(JobStruct), c_u32, c_u64, c_u64, P(c_u32), ctypes.c_size_t, c_u32, c_u32,
+                                      ctypes.c_char_p, P(JobShare), ctypes.c_size_t, P(JobSharesResult)],
+                                     ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -312,6 +344,116 @@ def roll_versions(base: int, count: int, mask: int = BIP320_MASK):
             v |= (i >> k & 1) << b
         out.append(v)
     return out
+
+
+def difficulty_to_target(difficulty) -> int:
+    """A pool's share difficulty as a target: floor(diff1 / difficulty), diff1 =
+    0xffff * 2^208, exact for the float's rational value and saturating at
+    2^256-1 (bm_target_from_difficulty, pure CPU); ValueError for a NaN, an
+    infinity or a value <= 0."""
+    if isinstance(difficulty, bool) or not isinstance(difficulty, (int, float)):
+        raise ValueError(f"difficulty must be a number, got {difficulty!r}")
+    try:
+        d = float(difficulty)
+    except OverflowError:
+        raise ValueError(f"difficulty {difficulty!r} does not fit a double") from None
+    buf = (ctypes.c_uint8 * 32)()
+    if load().bm_target_from_difficulty(d, buf) != BM_OK:
+        raise ValueError(f"difficulty must be a finite number above 0, got {difficulty!r}")
+    return int.from_bytes(bytes(buf), "big")
+
+
+def _hex_bytes(text, what, length=None) -> bytes:
+    try:
+        if not isinstance(text, str):
+            raise ValueError
+        raw = bytes.fromhex(text)
+    except ValueError:
+        raise ValueError(f"{what} must be a hex string, got {text!r}") from None
+    if length is not None and len(raw) != length:
+        raise ValueError(f"{what} must be {length} bytes, got {len(raw)}")
+    return raw
+
+
+def _u32(v, what) -> int:
+    if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U32_MAX:
+        raise ValueError(f"{what} must be in 0..2^32-1, got {v!r}")
+    return v
+
+
+class Job:
+    """A Stratum job (bm_job_t) that owns its buffers: the coinbase halves, the
+    miner's extranonce1, the size of extranonce2, the merkle branch (a list of
+    32-byte entries as sent), prevhash in header byte order, and version, nbits
+    and ntime as integers.  job_id is carried for submit_params only."""
+
+    def __init__(self, coinb1: bytes, extranonce1: bytes, extranonce2_size: int, coinb2: bytes, branch=(),
+                 prevhash: bytes = bytes(32), version: int = 0, nbits: int = 0, ntime: int = 0, job_id: str = ""):
+        self.coinb1, self.extranonce1, self.coinb2 = bytes(coinb1), bytes(extranonce1), bytes(coinb2)
+        self.branch = [bytes(b) for b in branch]
+        self.prevhash = bytes(prevhash)
+        if isinstance(extranonce2_size, bool) or not isinstance(extranonce2_size, int) or not 1 <= extranonce2_size <= 8:
+            raise ValueError(f"extranonce2_size must be in 1..8, got {extranonce2_size!r}")
+        if len(self.prevhash) != 32 or any(len(b) != 32 for b in self.branch):
+            raise ValueError("prevhash and every branch entry are 32 bytes")
+        if len(self.branch) > BM_MAX_JOB_BRANCH:
+            raise ValueError(f"at most {BM_MAX_JOB_BRANCH} branch entries, got {len(self.branch)}")
+        if len(self.coinb1) + len(self.extranonce1) + extranonce2_size + len(self.coinb2) > BM_MAX_JOB_COINBASE:
+            raise ValueError(f"the coinbase is longer than {BM_MAX_JOB_COINBASE} bytes")
+        self.extranonce2_size = extranonce2_size
+        self.version, self.nbits, self.ntime = _u32(version, "version"), _u32(nbits, "nbits"), _u32(ntime, "ntime")
+        self.job_id = job_id
+        self._branch = b"".join(self.branch)
+        self.struct = JobStruct(self.coinb1, len(self.coinb1), self.extranonce1, len(self.extranonce1),
+                                extranonce2_size, self.coinb2, len(self.coinb2), self._branch, len(self.branch),
+                                (ctypes.c_uint8 * 32)(*self.prevhash), self.version, self.nbits)
+
+    @classmethod
+    def from_notify(cls, params, extranonce1_hex: str, extranonce2_size: int):
+        """From the nine params of mining.notify (job id, prevhash, coinb1,
+        coinb2, merkle branch, version, nbits, ntime, clean_jobs) and what
+        mining.subscribe answered.  prevhash comes word-swapped and version,
+        nbits and ntime as big-endian hex, as Stratum sends them."""
+        params = list(params)
+        if len(params) != 9:
+            raise ValueError(f"mining.notify has 9 params, got {len(params)}")
+        job_id, prevhash, coinb1, coinb2, branch, version, nbits, ntime, _clean = params
+        if not isinstance(branch, (list, tuple)):
+            raise ValueError("the merkle branch must be a list of hex strings")
+        swapped = (ctypes.c_uint8 * 32)()
+        check(load().bm_job_prevhash_from_stratum(_hex_bytes(prevhash, "prevhash", 32), swapped),
+              "bm_job_prevhash_from_stratum")
+        words = [int.from_bytes(_hex_bytes(v, what, 4), "big")
+                 for v, what in ((version, "version"), (nbits, "nbits"), (ntime, "ntime"))]
+        return cls(_hex_bytes(coinb1, "coinb1"), _hex_bytes(extranonce1_hex, "extranonce1"), extranonce2_size,
+                   _hex_bytes(coinb2, "coinb2"), [_hex_bytes(b, "a branch entry", 32) for b in branch],
+                   bytes(swapped), words[0], words[1], words[2], job_id=str(job_id))
+
+    def _check_extranonce2(self, v, what="extranonce2"):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < 1 << (8 * self.extranonce2_size):
+            raise ValueError(f"{what} must be in 0..2^{8 * self.extranonce2_size}-1, got {v!r}")
+        return v
+
+    def header(self, extranonce2: int, ntime=None, version=None, nonce: int = 0) -> bytes:
+        """The 80-byte header of this job under extranonce2 (bm_job_header, pure
+        CPU); ntime and version default to the job's own."""
+        self._check_extranonce2(extranonce2)
+        ntime = _u32(self.ntime if ntime is None else ntime, "ntime")
+        version = _u32(self.version if version is None else version, "version")
+        buf = (ctypes.c_uint8 * HEADER_BYTES)()
+        check(load().bm_job_header(ctypes.byref(self.struct), extranonce2, ntime, version, buf), "bm_job_header")
+        return bytes(buf)[:76] + _u32(nonce, "nonce").to_bytes(4, "little")
+
+
+def submit_params(worker: str, job_id: str, share, mask: int = BIP320_MASK):
+    """mining.submit's params for a share of Context.search_job_shares (a dict
+    with extranonce2, extranonce2_size, ntime, nonce and version): [worker, job
+    id, extranonce2, ntime, nonce, version bits], all hex; the last is BIP 310's
+    version_bits, the share's version under the negotiated mask."""
+    _u32(mask, "mask")
+    size = share["extranonce2_size"]
+    return [worker, job_id, "%0*x" % (2 * size, share["extranonce2"]), "%08x" % share["ntime"],
+            "%08x" % share["nonce"], "%08x" % (share["version"] & mask)]
 
 
 def _header_bytes(header) -> bytes:
@@ -549,6 +691,51 @@ class Context:
             hits = [(int.from_bytes(raw[o:o + 32], "big"), int.from_bytes(raw[o + 32:o + 36], "little"),
                      int.from_bytes(raw[o + 36:o + 40], "little")) for o in range(0, len(raw), size)]
         return r.count, hits, (int.from_bytes(bytes(r.hash), "big"), r.nonce, r.version_index)
+
+    def search_job_shares(self, job, versions, en2_lo: int, en2_hi: int, nonce_lo: int = 0, nonce_hi: int = U32_MAX,
+                          target=U256_MAX, cap: int = 65536, ntime=None):
+        """A Stratum job under every extranonce2 of [en2_lo, en2_hi] (at most
+        4096 values) and each of `versions`: every (extranonce2, nonce, version
+        index) whose header hash is <= target -> (count, shares, best).  shares
+        is a list of dicts (hash, extranonce2, extranonce2_size, ntime, nonce,
+        version_index, version, is_block) ascending by (extranonce2, nonce,
+        index), or None when count > cap (nothing is returned then; count is
+        still exact, over the whole call); best is (hash, extranonce2, nonce,
+        index), the minimum of (hash >> 192, extranonce2, nonce, index).  cap =
+        0 only counts.  ntime defaults to the job's.  An empty range gives
+        (0, [], (2^256-1, en2_lo, 2^32-1, 0))."""
+        if not isinstance(job, Job):
+            raise ValueError("job must be a Job")
+        versions = list(versions)
+        if not 1 <= len(versions) <= BM_MAX_HEADER_VERSIONS:
+            raise ValueError(f"1..{BM_MAX_HEADER_VERSIONS} versions, got {len(versions)}")
+        for v, what in [(nonce_lo, "nonce_lo"), (nonce_hi, "nonce_hi")] + [(v, "a version") for v in versions]:
+            _u32(v, what)
+        ntime = _u32(job.ntime if ntime is None else ntime, "ntime")
+        for v, what in ((en2_lo, "en2_lo"), (en2_hi, "en2_hi")):
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U64_MAX:
+                raise ValueError(f"{what} must be in 0..2^64-1, got {v!r}")
+        if en2_lo <= en2_hi:
+            job._check_extranonce2(en2_hi, "en2_hi")
+            if en2_hi - en2_lo >= BM_MAX_JOB_HEADERS:
+                raise ValueError(f"at most {BM_MAX_JOB_HEADERS} extranonce2 values per call, "
+                                 f"got {en2_hi - en2_lo + 1}")
+        tgt = _target_bytes(target)
+        if not isinstance(cap, int) or isinstance(cap, bool) or not 0 <= cap <= BM_MAX_HEADER_HITS:
+            raise ValueError(f"cap must be in 0..{BM_MAX_HEADER_HITS}, got {cap!r}")
+        arr = (c_u32 * len(versions))(*versions)
+        r = JobSharesResult()
+        buf = (JobShare * cap)() if cap > 0 else None
+        check(self._lib.bm_search_job_shares_gpu(self.handle, ctypes.byref(job.struct), ntime, en2_lo, en2_hi, arr,
+                                                 len(versions), nonce_lo, nonce_hi, tgt, buf, cap, ctypes.byref(r)),
+              "bm_search_job_shares_gpu")
+        shares = None
+        if r.count <= cap:
+            shares = [{"hash": int.from_bytes(bytes(s.hash), "big"), "extranonce2": s.extranonce2,
+                       "extranonce2_size": job.extranonce2_size, "ntime": s.ntime, "nonce": s.nonce,
+                       "version_index": s.version_index, "version": s.version, "is_block": bool(s.is_block)}
+                      for s in (buf[i] for i in range(r.stored))]
+        return r.count, shares, (int.from_bytes(bytes(r.hash), "big"), r.extranonce2, r.nonce, r.version_index)
 
     def search_header_hits(self, header: bytes, nonce_lo: int = 0, nonce_hi: int = U32_MAX, target=U256_MAX,
                            cap: int = 4096):

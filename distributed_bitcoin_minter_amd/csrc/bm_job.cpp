@@ -1,0 +1,72 @@
+// bm_job.cpp -- the pure-CPU entries of the Stratum job layer (include/btcminer.h):
+// bm_job_prevhash_from_stratum, bm_job_header, bm_target_from_difficulty.  They
+// need no context and no GPU; bm_search_job_shares_gpu (bm_search.cpp) builds
+// its headers with the same code (bm_job.hpp).  Plain C++: no HIP in here.
+#include "bm_job.hpp"
+
+#include <cmath>
+
+extern "C" {
+
+int bm_job_prevhash_from_stratum(const uint8_t in[32], uint8_t out[32]) {
+    if (!in || !out) return BM_EINVAL;
+    uint8_t t[32];  // in and out may be the same array
+    for (int w = 0; w < 8; ++w)
+        for (int b = 0; b < 4; ++b) t[4 * w + b] = in[4 * w + 3 - b];
+    std::memcpy(out, t, sizeof t);
+    return BM_OK;
+}
+
+int bm_job_header(const bm_job_t* job, uint64_t extranonce2, uint32_t ntime, uint32_t version, uint8_t header[80]) {
+    if (!header) return BM_EINVAL;
+    const int rc = bm::host::job_check(job);
+    if (rc != BM_OK) return rc;
+    if (!bm::host::extranonce2_fits(extranonce2, job->extranonce2_size)) return BM_EINVAL;
+    uint8_t h[bm::kHeaderBytes];
+    bm::host::job_header(job, extranonce2, ntime, version, h);
+    std::memcpy(header, h, sizeof h);
+    return BM_OK;
+}
+
+// target = floor(diff1 / difficulty), diff1 = 0xffff * 2^208, for the double's
+// exact value m * 2^e (m a 53-bit integer): floor(0xffff * 2^(208 - e) / m), one
+// long division of a multi-word integer by m.
+int bm_target_from_difficulty(double difficulty, uint8_t target[32]) {
+    if (!target || !std::isfinite(difficulty) || !(difficulty > 0.0)) return BM_EINVAL;
+    int e = 0;
+    const double frac = std::frexp(difficulty, &e);          // difficulty = frac * 2^e, frac in [0.5, 1)
+    const uint64_t m = (uint64_t)std::ldexp(frac, 53);       // exact: 2^52 <= m < 2^53 (denormals too)
+    e -= 53;                                                 // difficulty = m * 2^e
+    const int shift = 208 - e;                               // the numerator is 0xffff << shift
+    std::memset(target, 0, 32);
+    if (shift < 0) return BM_OK;                             // 0xffff >> -shift is below m: the quotient is 0
+    // shift > 320: the quotient is above 2^(15 + 321 - 53) > 2^256
+    constexpr int kLimbs = 11;                               // 352 bits hold 0xffff << 320
+    uint32_t num[kLimbs] = {};                               // least significant limb first
+    bool saturate = shift > 320;
+    if (!saturate) {
+        const int limb = shift / 32, bit = shift % 32;
+        const uint64_t v = (uint64_t)0xffffu << bit;
+        num[limb] = (uint32_t)v;
+        if (limb + 1 < kLimbs) num[limb + 1] = (uint32_t)(v >> 32);
+        unsigned __int128 rem = 0;
+        uint32_t q[kLimbs];
+        for (int i = kLimbs - 1; i >= 0; --i) {
+            rem = (rem << 32) | num[i];                      // rem < m < 2^53 before: below 2^85 here
+            q[i] = (uint32_t)(rem / m);
+            rem %= m;
+        }
+        for (int i = 8; i < kLimbs; ++i) saturate = saturate || q[i] != 0;
+        if (!saturate)
+            for (int i = 0; i < 8; ++i) {
+                target[31 - 4 * i] = (uint8_t)q[i];
+                target[30 - 4 * i] = (uint8_t)(q[i] >> 8);
+                target[29 - 4 * i] = (uint8_t)(q[i] >> 16);
+                target[28 - 4 * i] = (uint8_t)(q[i] >> 24);
+            }
+    }
+    if (saturate) std::memset(target, 0xFF, 32);
+    return BM_OK;
+}
+
+}  // extern "C"

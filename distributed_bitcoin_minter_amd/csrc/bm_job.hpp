@@ -1,0 +1,213 @@
+// bm_job.hpp -- the host's half of bm_search_job_shares_gpu: a Stratum job
+// (coinbase halves, extranonce, merkle branch, prevhash, version, nbits) becomes
+// one 80-byte header per extranonce2 value, and the per-header answers of the
+// version-rolling share enumeration become one list and one best share
+// (JobMerge).  Shared by the launcher (bm_search.cpp), the pure-CPU entries
+// (bm_job.cpp) and a stand-alone CPU check (tools/job_check.cpp).  Plain C++:
+// no HIP in here.
+//
+//   coinbase = coinb1 || extranonce1 || BE(extranonce2, extranonce2_size) || coinb2
+//   root     = sha256d(coinbase); for each branch entry: root = sha256d(root || entry)
+//   header   = le32(version) || prevhash || root || le32(ntime) || le32(nbits) || 00000000
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "bm_header.hpp"
+#include "btcminer.h"
+
+namespace bm {
+namespace host {
+
+// SHA-256 of a byte stream fed in pieces, over compress_bytes.
+struct Sha256 {
+    uint32_t st[8];
+    uint8_t blk[64];
+    size_t fill = 0;
+    uint64_t total = 0;
+    Sha256() {
+        for (int i = 0; i < 8; ++i) st[i] = kIV256[i];
+    }
+    void update(const uint8_t* p, size_t n) {
+        total += n;
+        while (n > 0) {
+            const size_t take = n < 64 - fill ? n : 64 - fill;
+            std::memcpy(blk + fill, p, take);
+            fill += take;
+            p += take;
+            n -= take;
+            if (fill == 64) {
+                compress_bytes(st, blk);
+                fill = 0;
+            }
+        }
+    }
+    void finish(uint8_t digest[32]) {
+        const uint64_t bits = total * 8;
+        blk[fill++] = 0x80;
+        if (fill > 56) {  // no room for the length: it goes into a block of its own
+            std::memset(blk + fill, 0, 64 - fill);
+            compress_bytes(st, blk);
+            fill = 0;
+        }
+        std::memset(blk + fill, 0, 56 - fill);
+        for (int i = 0; i < 8; ++i) blk[56 + i] = (uint8_t)(bits >> (8 * (7 - i)));
+        compress_bytes(st, blk);
+        for (int i = 0; i < 8; ++i) {
+            digest[4 * i] = (uint8_t)(st[i] >> 24);
+            digest[4 * i + 1] = (uint8_t)(st[i] >> 16);
+            digest[4 * i + 2] = (uint8_t)(st[i] >> 8);
+            digest[4 * i + 3] = (uint8_t)st[i];
+        }
+    }
+};
+
+// digest = SHA256(SHA256(first)) of what h has been fed.
+inline void sha256d_finish(Sha256& h, uint8_t digest[32]) {
+    uint8_t first[32];
+    h.finish(first);
+    Sha256 second;
+    second.update(first, sizeof first);
+    second.finish(digest);
+}
+
+inline void store_le32(uint8_t* p, uint32_t v) {
+    p[0] = (uint8_t)v;
+    p[1] = (uint8_t)(v >> 8);
+    p[2] = (uint8_t)(v >> 16);
+    p[3] = (uint8_t)(v >> 24);
+}
+
+// extranonce2 fits its field: below 2^(8 * size), size in 1..8.
+inline bool extranonce2_fits(uint64_t extranonce2, uint32_t size) {
+    return size >= 8 || (extranonce2 >> (8 * size)) == 0;
+}
+
+// Everything bm_job_header refuses that does not depend on extranonce2.
+inline int job_check(const bm_job_t* job) {
+    if (!job) return BM_EINVAL;
+    if ((!job->coinb1 && job->coinb1_len) || (!job->extranonce1 && job->extranonce1_len) ||
+        (!job->coinb2 && job->coinb2_len) || (!job->branch && job->nbranch))
+        return BM_EINVAL;
+    if (job->extranonce2_size < 1 || job->extranonce2_size > 8) return BM_EINVAL;
+    if (job->nbranch > BM_MAX_JOB_BRANCH) return BM_EINVAL;
+    // each length against the limit first, so the sum cannot wrap
+    const size_t lim = BM_MAX_JOB_COINBASE;
+    if (job->coinb1_len > lim || job->extranonce1_len > lim || job->coinb2_len > lim) return BM_EINVAL;
+    if (job->coinb1_len + job->extranonce1_len + job->extranonce2_size + job->coinb2_len > lim) return BM_EINVAL;
+    return BM_OK;
+}
+
+// The header of a checked job (job_check, extranonce2_fits) with a zero nonce field.
+inline void job_header(const bm_job_t* job, uint64_t extranonce2, uint32_t ntime, uint32_t version,
+                       uint8_t header[kHeaderBytes]) {
+    uint8_t en2[8];
+    const uint32_t size = job->extranonce2_size;
+    for (uint32_t i = 0; i < size; ++i) en2[i] = (uint8_t)(extranonce2 >> (8 * (size - 1 - i)));
+    uint8_t root[32];
+    Sha256 h;
+    if (job->coinb1_len) h.update(job->coinb1, job->coinb1_len);
+    if (job->extranonce1_len) h.update(job->extranonce1, job->extranonce1_len);
+    h.update(en2, size);
+    if (job->coinb2_len) h.update(job->coinb2, job->coinb2_len);
+    sha256d_finish(h, root);
+    for (size_t b = 0; b < job->nbranch; ++b) {
+        Sha256 node;
+        node.update(root, sizeof root);
+        node.update(job->branch + 32 * b, 32);
+        sha256d_finish(node, root);
+    }
+    store_le32(header, version);
+    std::memcpy(header + 4, job->prevhash, 32);
+    std::memcpy(header + 36, root, 32);
+    store_le32(header + 68, ntime);
+    store_le32(header + 72, job->nbits);
+    store_le32(header + 76, 0);
+}
+
+// The per-header answers of one bm_search_job_shares_gpu call, in ascending
+// extranonce2 order, become its answer.  All or nothing over the whole call:
+// room() is the cap the next header's enumeration gets, what is left of the
+// call's cap while the running count fits in it and 0 (a pure count) from then
+// on; the list is kept here and reaches the caller's array in finish() only, so
+// a failure part-way leaves that array untouched.
+class JobMerge {
+public:
+    // block_target: the target of the job's nbits (most significant byte first),
+    // or nullptr when nbits does not decode (is_block stays 0)
+    JobMerge(size_t cap, const uint8_t* block_target, uint32_t ntime, uint64_t en2_lo, uint32_t version0)
+        : cap_(cap), ntime_(ntime), has_block_(block_target != nullptr) {
+        if (has_block_) std::memcpy(block_, block_target, sizeof block_);
+        std::memset(&out_, 0, sizeof out_);
+        std::memset(out_.hash, 0xFF, sizeof out_.hash);  // the empty answer
+        out_.extranonce2 = en2_lo;
+        out_.nonce = 0xFFFFFFFFu;
+        out_.version = version0;
+    }
+
+    size_t room() const { return out_.count <= cap_ ? cap_ - (size_t)out_.count : 0; }
+
+    // One header's answer: r and hits[0 .. r.stored) as header_versions_hits_impl
+    // left them for a call with cap room().  BM_EINTERNAL unless stored is what
+    // all-or-nothing allows and the entries ascend by (nonce, index).
+    int add(uint64_t extranonce2, const bm_header_version_hit_t* hits, const bm_header_versions_hits_result_t& r) {
+        const size_t room_now = room();
+        if (r.stored != (r.count <= room_now ? r.count : 0)) return BM_EINTERNAL;
+        if (r.stored && !hits) return BM_EINTERNAL;
+        if (out_.headers > 0 && extranonce2 <= last_en2_) return BM_EINTERNAL;
+        for (size_t i = 1; i < r.stored; ++i)
+            if (pair_key(hits[i - 1]) >= pair_key(hits[i])) return BM_EINTERNAL;
+        out_.count += r.count;
+        if (out_.count > cap_) {
+            std::vector<bm_job_share_t>().swap(list_);  // over the cap for good: only counts from here
+        } else {
+            for (size_t i = 0; i < r.stored; ++i) {
+                bm_job_share_t s;
+                std::memcpy(s.hash, hits[i].hash, sizeof s.hash);
+                s.extranonce2 = extranonce2;
+                s.nonce = hits[i].nonce;
+                s.ntime = ntime_;
+                s.version_index = hits[i].version_index;
+                s.version = hits[i].version;
+                s.is_block = has_block_ && std::memcmp(s.hash, block_, 32) <= 0 ? 1 : 0;
+                s.reserved = 0;
+                list_.push_back(s);
+            }
+        }
+        // the best share minimises (hash >> 192, extranonce2, nonce, index): headers
+        // come in ascending extranonce2 order, so a later one wins on a smaller hash only
+        if (out_.headers == 0 || hash_top64(r.hash) < hash_top64(out_.hash)) {
+            std::memcpy(out_.hash, r.hash, sizeof out_.hash);
+            out_.extranonce2 = extranonce2;
+            out_.nonce = r.nonce;
+            out_.version_index = r.version_index;
+            out_.version = r.version;
+        }
+        last_en2_ = extranonce2;
+        ++out_.headers;
+        return BM_OK;
+    }
+
+    // The call's answer: shares[0 .. stored) (never more than the cap) and *out.
+    void finish(bm_job_share_t* shares, bm_job_shares_result_t* out) {
+        out_.stored = out_.count <= cap_ ? list_.size() : 0;
+        if (out_.stored) std::memcpy(shares, list_.data(), list_.size() * sizeof(bm_job_share_t));
+        *out = out_;
+    }
+
+private:
+    static uint64_t pair_key(const bm_header_version_hit_t& h) { return ((uint64_t)h.nonce << 32) | h.version_index; }
+
+    size_t cap_;
+    uint32_t ntime_;
+    bool has_block_;
+    uint8_t block_[32];
+    uint64_t last_en2_ = 0;
+    std::vector<bm_job_share_t> list_;
+    bm_job_shares_result_t out_;
+};
+
+}  // namespace host
+}  // namespace bm

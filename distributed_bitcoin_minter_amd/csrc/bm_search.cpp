@@ -1,7 +1,8 @@
 // bm_search.cpp -- the seven searches of include/btcminer.h (bm_search_gpu,
 // bm_search_target_gpu, bm_search_hits_gpu, bm_search_header_gpu,
 // bm_search_header_hits_gpu, bm_search_header_versions_gpu,
-// bm_search_header_versions_hits_gpu) over one path: plan and size every
+// bm_search_header_versions_hits_gpu) over one path, and bm_search_job_shares_gpu,
+// a host loop over the last of them (job_shares_impl).  The path: plan and size every
 // launch, enqueue each device's launches and its second-pass reduction,
 // combine the devices' partials, read back what an enumeration appended,
 // record the stats.  run_call drives that path for the six searches outside a
@@ -21,6 +22,7 @@
 
 #include "bm_header_hits.hpp"
 #include "bm_header_versions_hits.hpp"
+#include "bm_job.hpp"
 #include "bm_runtime.hpp"
 
 namespace bm {
@@ -968,6 +970,39 @@ int header_versions_hits_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t
     return BM_OK;
 }
 
+// bm_search_job_shares_gpu: no kernel of its own.  One header per extranonce2
+// value of [en2_lo, en2_hi], ascending (host::job_header), each scanned by
+// header_versions_hits_impl with what is left of the call's cap (0, a pure
+// count, once the running count has passed it); host::JobMerge keeps the list
+// and the best share until the last header has succeeded, so a failure
+// part-way leaves shares and out untouched.  An empty range runs one empty
+// inner call, so the stats are those of the last inner call either way.
+int job_shares_impl(bm_ctx* ctx, const bm_job_t* job, uint32_t ntime, uint64_t en2_lo, uint64_t en2_hi,
+                    const uint32_t* versions, size_t nver, uint32_t lo, uint32_t hi, const uint8_t* target,
+                    bm_job_share_t* shares, size_t cap, bm_job_shares_result_t* out) {
+    uint8_t block[32];
+    const bool has_block = host::target_from_bits(job->nbits, block);
+    host::JobMerge merge(cap, has_block ? block : nullptr, ntime, en2_lo, versions[0]);
+    bm_header_versions_hits_result_t r;
+    uint8_t header[kHeaderBytes] = {};
+    if (en2_lo > en2_hi || lo > hi) {
+        BM_TRY(header_versions_hits_impl(ctx, header, versions, nver, 1, 0, target, nullptr, 0, &r));
+        merge.finish(shares, out);
+        return BM_OK;
+    }
+    std::unique_ptr<bm_header_version_hit_t[]> hits;  // one header's list: at most cap entries
+    if (cap > 0) hits.reset(new bm_header_version_hit_t[cap]);
+    for (uint64_t e = en2_lo;; ++e) {  // ends on e == en2_hi: en2_hi + 1 may wrap
+        host::job_header(job, e, ntime, versions[0], header);
+        BM_TRY(header_versions_hits_impl(ctx, header, versions, nver, lo, hi, target, hits.get(), merge.room(), &r));
+        const int rc = merge.add(e, hits.get(), r);
+        if (rc != BM_OK) return fail_call(ctx, rc);
+        if (e == en2_hi) break;
+    }
+    merge.finish(shares, out);
+    return BM_OK;
+}
+
 // The tail of every bm_search_*_gpu once it has checked its arguments:
 // impl(&r) with the caller's current device kept and no exception leaving the
 // C ABI; *out is written on success only.
@@ -1050,6 +1085,25 @@ int bm_search_header_versions_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, con
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
     return bm::call_into(out, [&](bm_header_versions_hits_result_t* r) {
         return bm::header_versions_hits_impl(ctx, header, versions, nver, nonce_lo, nonce_hi, target, hits, cap, r);
+    });
+}
+
+int bm_search_job_shares_gpu(bm_ctx_t* ctx, const bm_job_t* job, uint32_t ntime, uint64_t en2_lo, uint64_t en2_hi,
+                             const uint32_t* versions, size_t nver, uint32_t nonce_lo, uint32_t nonce_hi,
+                             const uint8_t* target, bm_job_share_t* shares, size_t cap,
+                             bm_job_shares_result_t* out) {
+    if (!ctx || !job || !versions || !target || !out) return BM_EINVAL;
+    if (nver == 0 || nver > BM_MAX_HEADER_VERSIONS) return BM_EINVAL;
+    if (cap > BM_MAX_HEADER_HITS || (!shares && cap > 0)) return BM_EINVAL;
+    if (bm::host::job_check(job) != BM_OK) return BM_EINVAL;
+    if (en2_lo <= en2_hi) {
+        if (en2_hi - en2_lo >= BM_MAX_JOB_HEADERS) return BM_EINVAL;
+        if (!bm::host::extranonce2_fits(en2_hi, job->extranonce2_size)) return BM_EINVAL;
+    }
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    return bm::call_into(out, [&](bm_job_shares_result_t* r) {
+        return bm::job_shares_impl(ctx, job, ntime, en2_lo, en2_hi, versions, nver, nonce_lo, nonce_hi, target, shares,
+                                   cap, r);
     });
 }
 

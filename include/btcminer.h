@@ -268,9 +268,9 @@ int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t l
  * 8 * (exponent - 3), a right shift for exponents below 3.  BM_EINVAL when the
  * sign bit 0x00800000 is set or the value overflows 256 bits.
  *
- * Out of scope: rolling ntime or an extranonce past 2^32 nonces (the caller
- * changes the header and calls again; a call is a fraction of a second);
- * cancelling one device's work on another device's hit; rank groups; the LSP
+ * Rolling extranonce2 past 2^32 nonces is bm_search_job_shares_gpu, below.
+ * Out of scope: rolling ntime (the caller changes the header and calls again; a
+ * call is a fraction of a second); cancelling one device's work on another device's hit; rank groups; the LSP
  * server protocol. */
 #define BM_MAX_HEADER_HASHES (1u << 24)
 typedef struct bm_header_result {
@@ -322,8 +322,9 @@ int bm_header_target_from_bits(uint32_t nbits, uint8_t target[32]);
  * hit is one atomic on one word per device and, when stored, one sha256d on
  * the host.
  *
- * Out of scope: several headers in one call; extranonce or merkle rolling;
- * cancelling across devices; rank groups; the LSP server protocol. */
+ * Several headers in one call, with extranonce2 and merkle rolling, is
+ * bm_search_job_shares_gpu, below.
+ * Out of scope: cancelling across devices; rank groups; the LSP server protocol. */
 #define BM_MAX_HEADER_HITS (1u << 20) /* entries; each stored hit costs one host sha256d */
 typedef struct bm_header_hit {
     uint8_t hash[32]; /* H(nonce) */
@@ -379,8 +380,9 @@ int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t header[80], uint32_t 
  * counts (nonce, version) pairs in nonces_dispatched.
  *
  * Share enumeration across versions is bm_search_header_versions_hits_gpu, below.
- * Out of scope: ntime, extranonce or merkle rolling; cancelling across devices;
- * rank groups; the LSP server protocol. */
+ * Extranonce2 and merkle rolling is bm_search_job_shares_gpu, below.
+ * Out of scope: ntime rolling; cancelling across devices; rank groups; the LSP
+ * server protocol. */
 #define BM_MAX_HEADER_VERSIONS 64
 typedef struct bm_header_versions_result {
     uint8_t hash[32];       /* as bm_header_result_t: most significant byte first */
@@ -433,8 +435,9 @@ int bm_search_header_versions_gpu(bm_ctx_t* ctx, const uint8_t header[80], const
  * (nonce, version) pairs in nonces; bm_ctx_last_target_stats is not touched.
  * Cost: that of a full bm_search_header_versions_gpu scan while hits are rare.
  *
- * Out of scope: ntime, extranonce or merkle rolling; cancelling across devices;
- * rank groups; the LSP server protocol. */
+ * Extranonce2 and merkle rolling is bm_search_job_shares_gpu, below.
+ * Out of scope: ntime rolling; cancelling across devices; rank groups; the LSP
+ * server protocol. */
 typedef struct bm_header_version_hit {
     uint8_t hash[32];        /* H(version_index, nonce), most significant byte first */
     uint32_t nonce;
@@ -453,6 +456,107 @@ int bm_search_header_versions_hits_gpu(bm_ctx_t* ctx, const uint8_t header[80], 
                                        size_t nver, uint32_t nonce_lo, uint32_t nonce_hi, const uint8_t target[32],
                                        bm_header_version_hit_t* hits, size_t cap,
                                        bm_header_versions_hits_result_t* out);
+
+/* ---- Stratum jobs: extranonce2 rolling over the version-rolling shares -------
+ * A pool hands out a job, not a header: a coinbase in two halves, the miner's
+ * extranonce1, the size of extranonce2, a merkle branch, prevhash, version,
+ * nbits, ntime and a difficulty.  For a value of extranonce2
+ *   coinbase = coinb1 || extranonce1 || BE(extranonce2, extranonce2_size) || coinb2
+ *   root     = sha256d(coinbase); for each branch entry: root = sha256d(root || entry)
+ *   header   = le32(version) || prevhash || root || le32(ntime) || le32(nbits) || 00000000
+ * extranonce2 is serialised big-endian, so mining.submit's extranonce2 string is
+ * the zero-padded hex of the integer.  The branch entries are the 32 bytes of
+ * each hex string as sent (raw digest order).  prevhash holds bytes 4..35 of the
+ * header; mining.notify sends it with each 4-byte word reversed
+ * (bm_job_prevhash_from_stratum undoes that; in and out may be the same array).
+ *
+ * The three entries below are pure CPU: no context, no GPU.
+ * bm_job_header: the 80 bytes above.  BM_EINVAL for a NULL job or header, a NULL
+ *   pointer with a non-zero length, extranonce2_size outside 1..8, extranonce2 >=
+ *   2^(8 * size), nbranch > BM_MAX_JOB_BRANCH, or a coinbase longer than
+ *   BM_MAX_JOB_COINBASE; header is untouched then.
+ * bm_target_from_difficulty: target = floor(diff1 / difficulty), diff1 = 0xffff *
+ *   2^208 (the target of nbits 1d00ffff), exact for the double's rational value
+ *   (one big-integer division, no floating point in the quotient), saturating at
+ *   2^256 - 1; most significant byte first.  BM_EINVAL for a NaN, an infinity, a
+ *   value <= 0 or a NULL target.
+ *
+ * bm_search_job_shares_gpu: for every extranonce2 of [en2_lo, en2_hi], ascending,
+ * the header of (job, extranonce2, ntime) is scanned by the version-rolling share
+ * enumeration over versions[0 .. nver) and [nonce_lo, nonce_hi]: a host loop of
+ * bm_search_header_versions_hits_gpu's own call, one per header (job->version is
+ * not used: every header's version field comes from versions[]).  H, `hash` and
+ * `target` are as there: most significant byte first, compared over 256 bits.
+ *   shares[0 .. stored) holds every hit, ascending by (extranonce2, nonce,
+ *     version_index), each triple exactly once.  is_block = 1 when the hash is
+ *     also <= bm_header_target_from_bits(job->nbits); an nbits that does not
+ *     decode leaves it 0.  count is exact, always.
+ *   All or nothing over the whole call: count > cap writes NOTHING to shares,
+ *     stored = 0, and the call still succeeds with the exact count (once the
+ *     running count passes cap, the remaining headers run as pure counts).
+ *     shares == NULL with cap == 0 is a pure count.  cap > BM_MAX_HEADER_HITS, or
+ *     shares == NULL with cap > 0: BM_EINVAL.
+ *   out->hash / extranonce2 / nonce / version_index / version: the share
+ *     minimising (H >> 192, extranonce2, nonce, version_index) over everything
+ *     scanned, with its full hash.  headers = extranonce2 values scanned.
+ *   en2_lo > en2_hi or nonce_lo > nonce_hi: nothing is scanned: hash all 0xFF,
+ *     nonce = 0xFFFFFFFF, extranonce2 = en2_lo, version_index = 0, version =
+ *     versions[0], count = stored = headers = 0; shares untouched.
+ *   More than BM_MAX_JOB_HEADERS values in [en2_lo, en2_hi], or en2_hi >=
+ *     2^(8 * size): BM_EINVAL.  en2_hi = 2^64 - 1 with size 8 is legal.
+ * A NULL ctx, job, versions, target or out, nver == 0 or > BM_MAX_HEADER_VERSIONS,
+ * or a job bm_job_header refuses: BM_EINVAL, before anything else is
+ * dereferenced.  A rank context with world > 1: BM_EINVAL.  On any failure
+ * `shares` and `out` are untouched and the context stays usable.
+ * The result never depends on timing, residency, streams, BTCMINER_CHUNK, blocks
+ * per CU, the split or the grouping (BTCMINER_HEADER_GROUP): it is the inner
+ * call's, header by header.  bm_ctx_set_test_fault applies to each inner call.
+ * bm_ctx_last_stats describes the LAST inner call only (one header; an empty
+ * range: an empty inner call); bm_ctx_last_target_stats is not touched.
+ * Cost: headers x one bm_search_header_versions_hits_gpu call; building a header
+ * is two host hashes of the coinbase plus one per branch entry.
+ *
+ * Out of scope: a network Stratum client; ntime rolling inside the call;
+ * cancelling across devices; rank groups; the LSP server protocol. */
+#define BM_MAX_JOB_COINBASE (1u << 16) /* bytes of coinb1 + extranonce1 + extranonce2 + coinb2 */
+#define BM_MAX_JOB_BRANCH 32
+#define BM_MAX_JOB_HEADERS 4096        /* extranonce2 values per call */
+typedef struct bm_job {
+    const uint8_t* coinb1;
+    size_t coinb1_len;
+    const uint8_t* extranonce1;
+    size_t extranonce1_len;
+    uint32_t extranonce2_size; /* 1..8 bytes */
+    const uint8_t* coinb2;
+    size_t coinb2_len;
+    const uint8_t* branch;     /* nbranch * 32 bytes, as sent (raw digest order) */
+    size_t nbranch;
+    uint8_t prevhash[32];      /* header byte order (bytes 4..35 of the header) */
+    uint32_t version, nbits;   /* as integers: the header holds le32 of them */
+} bm_job_t;
+typedef struct bm_job_share {
+    uint8_t hash[32];          /* most significant byte first, recomputed on the host */
+    uint64_t extranonce2;
+    uint32_t nonce, ntime;
+    uint32_t version_index, version;
+    uint32_t is_block;         /* 1: hash also <= the target of job->nbits */
+    uint32_t reserved;         /* 0 */
+} bm_job_share_t;              /* 64 bytes */
+typedef struct bm_job_shares_result {
+    uint8_t hash[32];          /* best share over everything scanned */
+    uint64_t extranonce2;
+    uint32_t nonce, version_index, version, reserved;
+    uint64_t count, stored;
+    uint64_t headers;          /* extranonce2 values scanned */
+} bm_job_shares_result_t;      /* 80 bytes */
+
+int bm_job_prevhash_from_stratum(const uint8_t in[32], uint8_t out[32]);
+int bm_job_header(const bm_job_t* job, uint64_t extranonce2, uint32_t ntime, uint32_t version, uint8_t header[80]);
+int bm_target_from_difficulty(double difficulty, uint8_t target[32]);
+int bm_search_job_shares_gpu(bm_ctx_t* ctx, const bm_job_t* job, uint32_t ntime, uint64_t en2_lo, uint64_t en2_hi,
+                             const uint32_t* versions, size_t nver, uint32_t nonce_lo, uint32_t nonce_hi,
+                             const uint8_t target[32], bm_job_share_t* shares, size_t cap,
+                             bm_job_shares_result_t* out);
 
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */

@@ -6,6 +6,7 @@
 //
 //   btcminer::Context   RAII owner of a bm_ctx (one process over N GPUs, or
 //                       one rank of an RCCL group); errors are exceptions.
+//   btcminer::Job       a Stratum job that owns its buffers (bm_job_t).
 //   bitcoin::           the reference's `bitcoin` package for this path:
 //                       Hash (hash.go:11-15), MsgType / Message / NewRequest /
 //                       NewResult / NewJoin / String (message.go:5-60), with
@@ -49,6 +50,53 @@ struct Result {
     uint64_t hash = UINT64_MAX;
     uint64_t nonce = UINT64_MAX;
 };
+
+// A Stratum job that owns its buffers (bm_job_t borrows them): the coinbase
+// halves, the miner's extranonce1, the size of extranonce2, the merkle branch
+// (32 bytes per entry, as sent), prevhash in header byte order, and version,
+// nbits and ntime as integers.
+class Job {
+   public:
+    std::vector<uint8_t> coinb1, extranonce1, coinb2, branch;
+    uint32_t extranonce2_size = 4;
+    uint8_t prevhash[32] = {};
+    uint32_t version = 0, nbits = 0, ntime = 0;
+
+    // prevhash as mining.notify sends it: each 4-byte word reversed
+    void set_prevhash_from_stratum(const uint8_t in[32]) {
+        check(bm_job_prevhash_from_stratum(in, prevhash), "bm_job_prevhash_from_stratum");
+    }
+    // the C view of this job: valid while the job lives and its buffers do not change
+    bm_job_t view() const {
+        bm_job_t j;
+        std::memset(&j, 0, sizeof j);
+        j.coinb1 = coinb1.data();
+        j.coinb1_len = coinb1.size();
+        j.extranonce1 = extranonce1.data();
+        j.extranonce1_len = extranonce1.size();
+        j.extranonce2_size = extranonce2_size;
+        j.coinb2 = coinb2.data();
+        j.coinb2_len = coinb2.size();
+        j.branch = branch.data();
+        j.nbranch = branch.size() / 32;
+        std::memcpy(j.prevhash, prevhash, sizeof j.prevhash);
+        j.version = version;
+        j.nbits = nbits;
+        return j;
+    }
+    // the 80-byte header under extranonce2, with a zero nonce field: bm_job_header
+    void header(uint64_t extranonce2, uint32_t ntime_, uint32_t version_, uint8_t out[80]) const {
+        if (branch.size() % 32 != 0) throw Error(BM_EINVAL, "Job::header");
+        const bm_job_t j = view();
+        check(bm_job_header(&j, extranonce2, ntime_, version_, out), "bm_job_header");
+    }
+    void header(uint64_t extranonce2, uint8_t out[80]) const { header(extranonce2, ntime, version, out); }
+};
+
+// floor(diff1 / difficulty) as 32 bytes, most significant first: bm_target_from_difficulty
+inline void target_from_difficulty(double difficulty, uint8_t target[32]) {
+    check(bm_target_from_difficulty(difficulty, target), "bm_target_from_difficulty");
+}
 
 // Owns a bm_ctx.  Not thread-safe, like the C context (one per OS thread).
 class Context {
@@ -187,6 +235,26 @@ class Context {
               "bm_search_header_versions_hits_gpu");
         buf.resize(static_cast<size_t>(r.stored));
         hits = std::move(buf);
+        return r;
+    }
+    // a Stratum job under every extranonce2 of [en2_lo, en2_hi] and each of
+    // `versions`, at the job's ntime: every share with hash <= target, ascending
+    // by (extranonce2, nonce, index), into `shares` (resized to the result's
+    // `stored`: empty when count > cap, over the whole call), plus the exact
+    // count and the best share: bm_search_job_shares_gpu
+    bm_job_shares_result_t search_job_shares(const Job& job, uint64_t en2_lo, uint64_t en2_hi,
+                                             const std::vector<uint32_t>& versions, uint32_t nonce_lo,
+                                             uint32_t nonce_hi, const uint8_t target[32],
+                                             std::vector<bm_job_share_t>& shares, size_t cap) {
+        if (job.branch.size() % 32 != 0) throw Error(BM_EINVAL, "search_job_shares");
+        const bm_job_t j = job.view();
+        bm_job_shares_result_t r;
+        std::vector<bm_job_share_t> buf(cap);
+        check(bm_search_job_shares_gpu(ctx_, &j, job.ntime, en2_lo, en2_hi, versions.data(), versions.size(), nonce_lo,
+                                       nonce_hi, target, cap ? buf.data() : nullptr, cap, &r),
+              "bm_search_job_shares_gpu");
+        buf.resize(static_cast<size_t>(r.stored));
+        shares = std::move(buf);
         return r;
     }
     // the double SHA-256 of the header under each nonce, 32 bytes each, most
