@@ -11,11 +11,13 @@ re-built as gfx950 HIP kernels behind the C ABI in include/btcminer.h
 """
 from . import bitcoin, dist
 from ._lib import (BtcMinerError, Context, HeaderHit, HeaderHitsResult, HeaderVersionHit, HeaderVersionsHitsResult,
-                   HeaderVersionsResult, HitsResult, Job, JobShare, JobSharesResult, LIB_PATH, bits_to_target,
-                   device_count, difficulty_to_target, plan_segments, rccl_unique_id, roll_versions, submit_params)
+                   HeaderVersionsResult, HitsResult, Job, JobShare, JobSharesResult, JobSubmit, JobVerdict,
+                   JobVerifyResult, LIB_PATH, bits_to_target, device_count, difficulty_to_target, parse_submit,
+                   plan_segments, rccl_unique_id, roll_versions, submit_params, verify_submits_cpu)
 from .miner import Miner
 
 __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", "HeaderHitsResult",
            "HeaderVersionHit", "HeaderVersionsHitsResult", "HeaderVersionsResult", "HitsResult", "Job", "JobShare",
-           "JobSharesResult", "LIB_PATH", "bits_to_target", "device_count", "difficulty_to_target", "plan_segments", "rccl_unique_id",
-           "roll_versions", "submit_params"]
+           "JobSharesResult", "JobSubmit", "JobVerdict", "JobVerifyResult", "LIB_PATH", "bits_to_target", "device_count",
+           "difficulty_to_target", "parse_submit", "plan_segments", "rccl_unique_id", "roll_versions", "submit_params",
+           "verify_submits_cpu"]

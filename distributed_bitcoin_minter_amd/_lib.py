@@ -142,6 +142,42 @@ class JobSharesResult(ctypes.Structure):
                 ("version", c_u32), ("reserved", c_u32), ("count", c_u64), ("stored", c_u64), ("headers", c_u64)]
 
 
+BM_MAX_JOB_SUBMITS = 1 << 20
+BM_SUBMIT_SHARE, BM_SUBMIT_BLOCK, BM_SUBMIT_INVALID = 1, 2, 4
+
+
+class JobSubmit(ctypes.Structure):
+    """bm_job_submit_t: version is the full header version field."""
+    _fields_ = [("extranonce2", c_u64), ("ntime", c_u32), ("nonce", c_u32), ("version", c_u32), ("reserved", c_u32)]
+
+
+class JobVerdict(ctypes.Structure):
+    """bm_job_verdict_t: hash most significant byte first, status the OR of
+    BM_SUBMIT_SHARE / BM_SUBMIT_BLOCK / BM_SUBMIT_INVALID."""
+    _fields_ = [("hash", ctypes.c_uint8 * 32), ("status", c_u32), ("reserved", c_u32)]
+
+    @property
+    def value(self) -> int:
+        """The hash as an integer (all ones for an INVALID entry)."""
+        return int.from_bytes(bytes(self.hash), "big")
+
+    @property
+    def is_share(self) -> bool:
+        return bool(self.status & BM_SUBMIT_SHARE)
+
+    @property
+    def is_block(self) -> bool:
+        return bool(self.status & BM_SUBMIT_BLOCK)
+
+    @property
+    def is_invalid(self) -> bool:
+        return bool(self.status & BM_SUBMIT_INVALID)
+
+
+class JobVerifyResult(ctypes.Structure):
+    _fields_ = [("n", c_u64), ("shares", c_u64), ("blocks", c_u64), ("invalid", c_u64)]
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -232,6 +268,10 @@ def _open(path):
         "bm_search_job_shares_gpu": ([vp, P(JobStruct), c_u32, c_u64, c_u64, P(c_u32), ctypes.c_size_t, c_u32, c_u32,
                                       ctypes.c_char_p, P(JobShare), ctypes.c_size_t, P(JobSharesResult)],
                                      ctypes.c_int),
+        "bm_job_verify_cpu": ([P(JobStruct), ctypes.c_char_p, P(JobSubmit), ctypes.c_size_t, P(JobVerdict),
+                               P(JobVerifyResult)], ctypes.c_int),
+        "bm_job_verify_gpu": ([vp, P(JobStruct), ctypes.c_char_p, P(JobSubmit), ctypes.c_size_t, P(JobVerdict),
+                               P(JobVerifyResult)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -454,6 +494,86 @@ def submit_params(worker: str, job_id: str, share, mask: int = BIP320_MASK):
     size = share["extranonce2_size"]
     return [worker, job_id, "%0*x" % (2 * size, share["extranonce2"]), "%08x" % share["ntime"],
             "%08x" % share["nonce"], "%08x" % (share["version"] & mask)]
+
+
+def _hex_field(text, digits, what) -> int:
+    if not isinstance(text, str) or len(text) != digits or any(c not in "0123456789abcdefABCDEF" for c in text):
+        raise ValueError(f"{what} must be {digits} hex digits, got {text!r}")
+    return int(text, 16)
+
+
+def parse_submit(params, job, mask: int = BIP320_MASK):
+    """The inverse of submit_params: mining.submit's params as sent ([worker, job
+    id, extranonce2, ntime, nonce] and, with version rolling, version bits) ->
+    a dict with extranonce2, extranonce2_size, ntime, nonce and version, the full
+    header version (job.version & ~mask) | bits; five params give job.version.
+    ValueError, with the reason first, for a wrong param count ("malformed"),
+    another job's id ("job-id"), an extranonce2 that is not 2 * extranonce2_size
+    hex digits ("extranonce2"), a field that is not 8 hex digits ("malformed") or
+    version bits outside the mask ("version-bits")."""
+    _u32(mask, "mask")
+    if not isinstance(params, (list, tuple)) or len(params) not in (5, 6):
+        raise ValueError("malformed: mining.submit has 5 or 6 params")
+    if params[1] != job.job_id:
+        raise ValueError(f"job-id: the job is {job.job_id!r}, got {params[1]!r}")
+    try:
+        en2 = _hex_field(params[2], 2 * job.extranonce2_size, "extranonce2")
+    except ValueError as e:
+        raise ValueError(f"extranonce2: {e}") from None
+    try:
+        ntime, nonce = _hex_field(params[3], 8, "ntime"), _hex_field(params[4], 8, "nonce")
+        bits = _hex_field(params[5], 8, "version bits") if len(params) == 6 else None
+    except ValueError as e:
+        raise ValueError(f"malformed: {e}") from None
+    version = job.version
+    if bits is not None:
+        if bits & ~mask:
+            raise ValueError(f"version-bits: {bits:08x} has bits outside the mask {mask:08x}")
+        version = (job.version & ~mask & U32_MAX) | bits
+    return {"extranonce2": en2, "extranonce2_size": job.extranonce2_size, "ntime": ntime, "nonce": nonce,
+            "version": version}
+
+
+def _submit_array(submits):
+    """A (JobSubmit * n) array from one (used as it is) or from an iterable of
+    dicts (extranonce2, ntime, nonce, version: parse_submit's, or the shares of
+    Context.search_job_shares) or (extranonce2, ntime, nonce, version) tuples."""
+    if isinstance(submits, ctypes.Array) and submits._type_ is JobSubmit:
+        return submits
+    rows = []
+    for s in submits:
+        row = tuple(s[k] for k in ("extranonce2", "ntime", "nonce", "version")) if isinstance(s, dict) else tuple(s)
+        if len(row) != 4:
+            raise ValueError(f"a submission is (extranonce2, ntime, nonce, version), got {s!r}")
+        if not isinstance(row[0], int) or isinstance(row[0], bool) or not 0 <= row[0] <= U64_MAX:
+            raise ValueError(f"extranonce2 must be in 0..2^64-1, got {row[0]!r}")
+        for v, what in zip(row[1:], ("ntime", "nonce", "version")):
+            _u32(v, what)
+        rows.append(row)
+    arr = (JobSubmit * len(rows))()
+    for a, row in zip(arr, rows):
+        a.extranonce2, a.ntime, a.nonce, a.version = row
+    return arr
+
+
+def _verify(call, what, job, submits, target):
+    if not isinstance(job, Job):
+        raise ValueError("job must be a Job")
+    arr = _submit_array(submits)
+    if len(arr) > BM_MAX_JOB_SUBMITS:
+        raise ValueError(f"at most {BM_MAX_JOB_SUBMITS} submissions per call, got {len(arr)}")
+    tgt = _target_bytes(target)
+    verdicts = (JobVerdict * len(arr))()
+    r = JobVerifyResult()
+    check(call(ctypes.byref(job.struct), tgt, arr if len(arr) else None, len(arr), verdicts if len(arr) else None,
+               ctypes.byref(r)), what)
+    return verdicts, r
+
+
+def verify_submits_cpu(job, submits, target):
+    """Context.verify_submits without a GPU or a context (bm_job_verify_cpu, pure
+    CPU): the specification of the GPU entry, byte-identical to it."""
+    return _verify(load().bm_job_verify_cpu, "bm_job_verify_cpu", job, submits, target)
 
 
 def _header_bytes(header) -> bytes:
@@ -736,6 +856,20 @@ class Context:
                        "version_index": s.version_index, "version": s.version, "is_block": bool(s.is_block)}
                       for s in (buf[i] for i in range(r.stored))]
         return r.count, shares, (int.from_bytes(bytes(r.hash), "big"), r.extranonce2, r.nonce, r.version_index)
+
+    def verify_submits(self, job, submits, target):
+        """A batch of mining.submit tuples of a Stratum job against a share
+        target, one GPU lane per submission (bm_job_verify_gpu, at most 2^20 per
+        call) -> (verdicts, result).  submits: a (JobSubmit * n) array, or an
+        iterable of dicts with extranonce2, ntime, nonce and version (the full
+        header version: parse_submit's answer, or a share of search_job_shares)
+        or of such 4-tuples.  verdicts is a (JobVerdict * n) array in the
+        caller's order: hash (.value as an integer) and status (is_share: hash
+        <= target; is_block: hash <= the target of the job's nbits; is_invalid:
+        extranonce2 does not fit its field, nothing hashed); result is a
+        JobVerifyResult with n and the count of each flag."""
+        return _verify(lambda *a: self._lib.bm_job_verify_gpu(self.handle, *a), "bm_job_verify_gpu", job, submits,
+                       target)
 
     def search_header_hits(self, header: bytes, nonce_lo: int = 0, nonce_hi: int = U32_MAX, target=U256_MAX,
                            cap: int = 4096):

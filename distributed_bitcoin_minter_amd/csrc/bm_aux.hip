@@ -1,13 +1,16 @@
 // bm_aux.hip -- the one unit of the host runtime with device code: the small
 // kernels of bm_aux_kernels.hpp, the host wrapper the searches launch the
 // second-pass reduction through, and the entry points outside the search
-// path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu).  See bm_runtime.hpp
-// for the layout of the host runtime.
+// path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu, and bm_job_verify_gpu,
+// whose kernel has a unit of its own, bm_job_verify_inst.hip).  See
+// bm_runtime.hpp for the layout of the host runtime.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <vector>
 
 #include "bm_aux_kernels.hpp"
+#include "bm_job.hpp"
 #include "bm_runtime.hpp"
 
 namespace bm {
@@ -122,10 +125,81 @@ int header_hash_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* nonces,
     return BM_OK;
 }
 
+// job_verify_kernel, registered by bm_job_verify_inst.hip at load time
+const void* g_job_verify = nullptr;
+
+// bm_job_verify_gpu on the first device: the job's tail template, its branch and
+// the submissions go up in one copy, one launch gives a lane to each submission,
+// the verdicts come back in one copy.  The caller's arrays are written last.
+int job_verify_impl(bm_ctx* ctx, const bm_job_t* job, const uint8_t* target, const bm_job_submit_t* submits, size_t n,
+                    bm_job_verdict_t* verdicts, bm_job_verify_result_t* out) {
+    if (!g_job_verify) return BM_EINTERNAL;
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    JobVerifyArgs A;
+    std::vector<uint32_t> tail, branch;
+    host::verify_prepare(job, target, A, tail, branch);
+    A.n = (uint32_t)n;
+    // device buffer, in 8-byte units: tail | branch | submits | verdicts
+    const size_t tail_u = tail.size() / 2, branch_u = branch.size() / 2;
+    const size_t sub_u = n * sizeof(bm_job_submit_t) / 8, in_u = tail_u + branch_u + sub_u;
+    const size_t out_u = n * sizeof(bm_job_verdict_t) / 8;
+    // and a pinned host copy of the same layout: the staging of the one copy up and the target of the one
+    // copy back (kept with the context: a batch is tens of megabytes, and fresh pageable memory per call
+    // costs more than the kernel)
+    BM_TRY(grow(d, d.h_verify, d.hverify_cap, in_u + out_u, sizeof(uint64_t), true));
+    BM_TRY(grow(d, d.d_verify, d.verify_cap, in_u + out_u));
+    uint64_t* stage = d.h_verify;
+    const bm_job_verdict_t* got = reinterpret_cast<const bm_job_verdict_t*>(d.h_verify + in_u);
+    std::memcpy(stage, tail.data(), 8 * tail_u);
+    if (branch_u) std::memcpy(stage + tail_u, branch.data(), 8 * branch_u);
+    std::memcpy(stage + tail_u + branch_u, submits, 8 * sub_u);
+    BM_HIP(hipMemcpyAsync(d.d_verify, stage, 8 * in_u, hipMemcpyHostToDevice, d.stream));
+    const uint32_t* d_tail = reinterpret_cast<const uint32_t*>(d.d_verify);
+    const uint32_t* d_branch = reinterpret_cast<const uint32_t*>(d.d_verify + tail_u);
+    const bm_job_submit_t* d_sub = reinterpret_cast<const bm_job_submit_t*>(d.d_verify + tail_u + branch_u);
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(d.d_verify + in_u);
+    const uint32_t grid = (uint32_t)((n + 63) / 64);
+    void* args[] = {&A, &d_tail, &d_branch, &d_sub, &d_out};
+    BM_HIP(hipLaunchKernel(g_job_verify, dim3(grid), dim3(64), args, 0, d.stream));
+    BM_HIP(hipMemcpyAsync(d.h_verify + in_u, d_out, 8 * out_u, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    // the tripwire: the ends of the batch and every claimed block, by the CPU path
+    uint8_t bt[32];
+    const uint8_t* block_target = host::target_from_bits(job->nbits, bt) ? bt : nullptr;
+    for (size_t i = 0; i < n; ++i) {
+        if (i != 0 && i != n - 1 && !(got[i].status & BM_SUBMIT_BLOCK)) continue;
+        bm_job_verdict_t want;
+        host::verify_one(job, target, block_target, submits[i], want);
+        if (std::memcmp(&want, &got[i], sizeof want) != 0) return BM_EINTERNAL;
+    }
+    bm_job_verify_result_t r;
+    host::verify_count(got, n, r);
+    std::memcpy(verdicts, got, n * sizeof(bm_job_verdict_t));
+    *out = r;
+    return BM_OK;
+}
+
 }  // namespace
 }  // namespace bm
 
 extern "C" {
+
+void bm_register_job_verify_kernel(const void* fn) { bm::g_job_verify = fn; }
+
+int bm_job_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const uint8_t* target, const bm_job_submit_t* submits,
+                      size_t n, bm_job_verdict_t* verdicts, bm_job_verify_result_t* out) {
+    if (!ctx) return BM_EINVAL;
+    const int rc = bm::host::verify_check(job, target, submits, n, verdicts, out);
+    if (rc != BM_OK) return rc;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    if (n == 0) {
+        std::memset(out, 0, sizeof *out);
+        return BM_OK;
+    }
+    bm::DeviceGuard guard;
+    return bm::guarded([&] { return bm::job_verify_impl(ctx, job, target, submits, n, verdicts, out); });
+}
 
 int bm_reduce_gpu(bm_ctx_t* ctx, const bm_result_t* parts, size_t n, bm_result_t* out) {
     if (!ctx || !out || (n && !parts) || n > BM_MAX_REDUCE) return BM_EINVAL;

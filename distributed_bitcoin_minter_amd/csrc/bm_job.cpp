@@ -1,7 +1,9 @@
 // bm_job.cpp -- the pure-CPU entries of the Stratum job layer (include/btcminer.h):
-// bm_job_prevhash_from_stratum, bm_job_header, bm_target_from_difficulty.  They
-// need no context and no GPU; bm_search_job_shares_gpu (bm_search.cpp) builds
-// its headers with the same code (bm_job.hpp).  Plain C++: no HIP in here.
+// bm_job_prevhash_from_stratum, bm_job_header, bm_job_verify_cpu,
+// bm_target_from_difficulty.  They need no context and no GPU;
+// bm_search_job_shares_gpu (bm_search.cpp) builds its headers and
+// bm_job_verify_gpu (bm_aux.hip) checks its device with the same code
+// (bm_job.hpp).  Plain C++: no HIP in here.
 #include "bm_job.hpp"
 
 #include <cmath>
@@ -25,6 +27,19 @@ int bm_job_header(const bm_job_t* job, uint64_t extranonce2, uint32_t ntime, uin
     uint8_t h[bm::kHeaderBytes];
     bm::host::job_header(job, extranonce2, ntime, version, h);
     std::memcpy(header, h, sizeof h);
+    return BM_OK;
+}
+
+// The specification of bm_job_verify_gpu, and the verifier of a caller without a
+// GPU: one bm_job_header and one double hash per submission.
+int bm_job_verify_cpu(const bm_job_t* job, const uint8_t target[32], const bm_job_submit_t* submits, size_t n,
+                      bm_job_verdict_t* verdicts, bm_job_verify_result_t* out) {
+    const int rc = bm::host::verify_check(job, target, submits, n, verdicts, out);
+    if (rc != BM_OK) return rc;
+    uint8_t bt[32];
+    const uint8_t* block_target = bm::host::target_from_bits(job->nbits, bt) ? bt : nullptr;
+    for (size_t i = 0; i < n; ++i) bm::host::verify_one(job, target, block_target, submits[i], verdicts[i]);
+    bm::host::verify_count(verdicts, n, *out);
     return BM_OK;
 }
 

@@ -2,9 +2,12 @@
 // (coinbase halves, extranonce, merkle branch, prevhash, version, nbits) becomes
 // one 80-byte header per extranonce2 value, and the per-header answers of the
 // version-rolling share enumeration become one list and one best share
-// (JobMerge).  Shared by the launcher (bm_search.cpp), the pure-CPU entries
-// (bm_job.cpp) and a stand-alone CPU check (tools/job_check.cpp).  Plain C++:
-// no HIP in here.
+// (JobMerge).  And the host's half of share verification (bm_job_verify_cpu,
+// bm_job_verify_gpu): one submission's verdict on the CPU, and what
+// job_verify_kernel (bm_job_verify.hpp) takes of a job.  Shared by the launcher
+// (bm_search.cpp), bm_aux.hip, the pure-CPU entries (bm_job.cpp) and two
+// stand-alone CPU checks (tools/job_check.cpp, tools/verify_check.cpp).  Plain
+// C++: no HIP in here (en2_words alone is marked for both sides).
 //
 //   coinbase = coinb1 || extranonce1 || BE(extranonce2, extranonce2_size) || coinb2
 //   root     = sha256d(coinbase); for each branch entry: root = sha256d(root || entry)
@@ -125,6 +128,127 @@ inline void job_header(const bm_job_t* job, uint64_t extranonce2, uint32_t ntime
     store_le32(header + 68, ntime);
     store_le32(header + 72, job->nbits);
     store_le32(header + 76, 0);
+}
+
+}  // namespace host
+
+// ---- share verification (bm_job_verify_cpu / bm_job_verify_gpu) ----
+// The coinbase of every submission of a job differs in extranonce2's bytes only,
+// and those have a fixed size and position.  So the host hashes the whole 64-byte
+// blocks that end before extranonce2's first byte once (mid), and lays the rest
+// out as a padded tail of big-endian words with extranonce2's bytes zero; a lane
+// ORs its extranonce2 into the up to three consecutive words it can touch (8
+// bytes at byte 1..3 of a word span three words, and may span a block edge).
+
+// Kernel argument of job_verify_kernel, by value (SGPRs).
+struct JobVerifyArgs {
+    uint32_t mid[8];    // state after the whole blocks before extranonce2's block
+    uint32_t prev[8];   // prevhash as big-endian words (header words 1..8)
+    uint32_t tgt[8];    // the share target, most significant word first
+    uint32_t btgt[8];   // the target of nbits, likewise (has_block)
+    uint32_t nbits;
+    uint32_t has_block; // 1: nbits decodes
+    uint32_t nb;        // 64-byte blocks of the tail (1..1025)
+    uint32_t j0;        // first tail word extranonce2 touches (0..15)
+    uint32_t boff;      // extranonce2's byte offset in that word (0..3)
+    uint32_t size;      // extranonce2_size (1..8)
+    uint32_t depth;     // branch entries (0..32)
+    uint32_t n;         // submissions
+};
+
+// A verdict as the kernel stores it: ten 32-bit words in bm_job_verdict_t's layout.
+constexpr int kVerdictWords = 10;
+static_assert(sizeof(bm_job_verdict_t) == 4 * kVerdictWords, "verdict layout");
+static_assert(sizeof(bm_job_submit_t) == 24, "submit layout");
+
+// extranonce2 (size bytes, big-endian) at byte boff of a 12-byte window, as the
+// window's three big-endian words.
+BM_HD inline void en2_words(uint64_t extranonce2, uint32_t size, uint32_t boff, uint32_t& e0, uint32_t& e1,
+                            uint32_t& e2) {
+    const uint64_t v = extranonce2 << (8 * (8 - size));  // its first byte on top
+    e0 = (uint32_t)(v >> (32 + 8 * boff));
+    e1 = (uint32_t)(v >> (8 * boff));
+    e2 = boff ? (uint32_t)(v << (32 - 8 * boff)) : 0u;
+}
+
+namespace host {
+
+// What job_verify_kernel takes of a checked job (job_check): A but for n, the
+// tail's words (16 * A.nb) and the branch's (8 * A.depth), both big-endian.
+inline void verify_prepare(const bm_job_t* job, const uint8_t target[32], JobVerifyArgs& A,
+                           std::vector<uint32_t>& tail, std::vector<uint32_t>& branch) {
+    std::memset(&A, 0, sizeof A);
+    const size_t pos = job->coinb1_len + job->extranonce1_len;  // extranonce2's first byte
+    const size_t size = job->extranonce2_size;
+    const size_t total = pos + size + job->coinb2_len;
+    const size_t pre = pos / 64;                                // whole blocks before its block
+    const size_t padded = (total + 9 + 63) / 64 * 64;
+    std::vector<uint8_t> bytes(padded, 0);
+    if (job->coinb1_len) std::memcpy(bytes.data(), job->coinb1, job->coinb1_len);
+    if (job->extranonce1_len) std::memcpy(bytes.data() + job->coinb1_len, job->extranonce1, job->extranonce1_len);
+    if (job->coinb2_len) std::memcpy(bytes.data() + pos + size, job->coinb2, job->coinb2_len);
+    bytes[total] = 0x80;
+    const uint64_t bits = (uint64_t)total * 8;
+    for (int i = 0; i < 8; ++i) bytes[padded - 8 + i] = (uint8_t)(bits >> (8 * (7 - i)));
+    uint32_t st[8];
+    for (int i = 0; i < 8; ++i) st[i] = kIV256[i];
+    for (size_t b = 0; b < pre; ++b) compress_bytes(st, bytes.data() + 64 * b);
+    for (int i = 0; i < 8; ++i) A.mid[i] = st[i];
+    A.nb = (uint32_t)(padded / 64 - pre);
+    const size_t off = pos - 64 * pre;
+    A.j0 = (uint32_t)(off / 4);
+    A.boff = (uint32_t)(off % 4);
+    A.size = (uint32_t)size;
+    A.depth = (uint32_t)job->nbranch;
+    tail.resize(16 * (size_t)A.nb);
+    for (size_t k = 0; k < tail.size(); ++k) tail[k] = load_be32(bytes.data() + 64 * pre + 4 * k);
+    branch.resize(8 * job->nbranch);
+    for (size_t k = 0; k < branch.size(); ++k) branch[k] = load_be32(job->branch + 4 * k);
+    for (int k = 0; k < 8; ++k) {
+        A.prev[k] = load_be32(job->prevhash + 4 * k);
+        A.tgt[k] = load_be32(target + 4 * k);
+    }
+    A.nbits = job->nbits;
+    uint8_t bt[32];
+    A.has_block = target_from_bits(job->nbits, bt) ? 1u : 0u;
+    if (A.has_block)
+        for (int k = 0; k < 8; ++k) A.btgt[k] = load_be32(bt + 4 * k);
+}
+
+// The verdict of one submission of a checked job.  block_target: the target of
+// the job's nbits, or nullptr when nbits does not decode.
+inline void verify_one(const bm_job_t* job, const uint8_t target[32], const uint8_t* block_target,
+                       const bm_job_submit_t& s, bm_job_verdict_t& v) {
+    std::memset(&v, 0, sizeof v);
+    if (!extranonce2_fits(s.extranonce2, job->extranonce2_size)) {
+        std::memset(v.hash, 0xFF, sizeof v.hash);
+        v.status = BM_SUBMIT_INVALID;
+        return;
+    }
+    uint8_t header[kHeaderBytes];
+    job_header(job, s.extranonce2, s.ntime, s.version, header);
+    header_hash_msb(header, s.nonce, v.hash);
+    if (std::memcmp(v.hash, target, 32) <= 0) v.status |= BM_SUBMIT_SHARE;
+    if (block_target && std::memcmp(v.hash, block_target, 32) <= 0) v.status |= BM_SUBMIT_BLOCK;
+}
+
+// *out of a call from its verdicts.
+inline void verify_count(const bm_job_verdict_t* verdicts, size_t n, bm_job_verify_result_t& out) {
+    std::memset(&out, 0, sizeof out);
+    out.n = n;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t st = verdicts[i].status;
+        out.shares += (st & BM_SUBMIT_SHARE) ? 1 : 0;
+        out.blocks += (st & BM_SUBMIT_BLOCK) ? 1 : 0;
+        out.invalid += (st & BM_SUBMIT_INVALID) ? 1 : 0;
+    }
+}
+
+// The arguments both entries refuse, ctx aside.
+inline int verify_check(const bm_job_t* job, const uint8_t* target, const bm_job_submit_t* submits, size_t n,
+                        const bm_job_verdict_t* verdicts, const bm_job_verify_result_t* out) {
+    if (!job || !target || !out || n > BM_MAX_JOB_SUBMITS || (n && (!submits || !verdicts))) return BM_EINVAL;
+    return job_check(job);
 }
 
 // The per-header answers of one bm_search_job_shares_gpu call, in ascending

@@ -5,7 +5,8 @@
 //   bm_search.cpp  the seven searches: kernel tables, sizing, one call driver, statistics
 //   bm_aux.hip     the only unit with device code: the kernels of bm_aux_kernels.hpp,
 //                  a host wrapper that launches the reduction, and the entry points
-//                  built on them (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu)
+//                  built on them (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu), and
+//                  bm_job_verify_gpu over job_verify_kernel (bm_job_verify_inst.hip)
 // The first three are plain C++ over the HIP host API.  DESIGN.md section 1.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -93,6 +94,9 @@ struct DeviceCtx {
     size_t hash_cap = 0;
     uint32_t* d_hdr_io = nullptr;  // bm_header_hash_gpu: n nonces, then 8 digest words per nonce
     size_t hdr_cap = 0;
+    uint64_t* d_verify = nullptr;  // bm_job_verify_gpu: tail template, branch, n submissions, then n verdicts
+    uint64_t* h_verify = nullptr;  // pinned copy of the same layout: staged for the copy up, target of the copy back
+    size_t verify_cap = 0, hverify_cap = 0;  // in 8-byte units
     hipEvent_t ev[2 * kEventPairs] = {};
     hipStream_t aux[kMaxStreams - 1] = {};  // extra launch streams (ctx->streams > 1)
     hipEvent_t fork = nullptr, join[kMaxStreams - 1] = {};

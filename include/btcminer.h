@@ -558,6 +558,73 @@ int bm_search_job_shares_gpu(bm_ctx_t* ctx, const bm_job_t* job, uint32_t ntime,
                              const uint8_t target[32], bm_job_share_t* shares, size_t cap,
                              bm_job_shares_result_t* out);
 
+/* ---- pool-side share verification: a batch of mining.submit tuples ------------
+ * What a pool, a proxy or a test of a miner does with the (extranonce2, ntime,
+ * nonce, version) tuples it receives for a job: rebuild each header, hash it and
+ * decide between an accepted share, a block and a reject.  Every submission needs
+ * a merkle root of its own (its coinbase under its extranonce2, the branch, the
+ * header's double hash: about 45 compressions under a 12-entry branch), so this
+ * is per-item work, and bm_job_verify_gpu gives one lane to each submission.
+ *
+ *   verdicts[i] belongs to submits[i]; the order is the caller's.
+ *   submits[i].version is the FULL header version field (a caller composes it
+ *     from the job's version and mining.submit's version bits); reserved is
+ *     ignored.
+ *   verdicts[i].hash = H of bm_job_header(job, extranonce2, ntime, version) with
+ *     nonce in bytes 76..79, most significant byte first like every header call.
+ *   verdicts[i].status = the OR of
+ *     BM_SUBMIT_SHARE   hash <= target,
+ *     BM_SUBMIT_BLOCK   hash <= bm_header_target_from_bits(job->nbits); an nbits
+ *                       that does not decode leaves it clear everywhere.  The two
+ *                       flags are independent: a share target below the block
+ *                       target can give BLOCK without SHARE,
+ *     BM_SUBMIT_INVALID extranonce2 >= 2^(8 * extranonce2_size): nothing is
+ *                       hashed, hash is all 0xFF and status is exactly this flag,
+ *     both compares over the full 256 bits.  verdicts[i].reserved = 0.
+ *   out: n and how many verdicts carry each flag.
+ *   n == 0 succeeds with a zero *out and touches neither array (both may be NULL).
+ * BM_EINVAL: n > BM_MAX_JOB_SUBMITS; a NULL job, target or out (or ctx); NULL
+ * submits or verdicts with n > 0; a job bm_job_header refuses; a rank context
+ * with world > 1.  On any failure `verdicts` and `out` are untouched and the
+ * context stays usable.
+ *
+ * bm_job_verify_cpu is pure CPU, no context: the specification, and what a
+ * caller without a GPU uses.  bm_job_verify_gpu gives byte-identical `verdicts`
+ * and `out`, on the first device of ctx (like bm_header_hash_gpu): one
+ * host-to-device copy (the job's tail template, its branch and the submissions),
+ * one launch of job_verify_kernel and one copy back, on that device's stream.
+ * The host then recomputes entry 0, entry n - 1 and every entry flagged BLOCK
+ * with the CPU path and returns BM_EINTERNAL on any difference: a tripwire, not
+ * the result -- everything else is the device's claim.  bm_ctx_last_stats is left
+ * as the previous call left it.
+ *
+ * Out of scope: duplicate detection across batches; an ntime window; vardiff; a
+ * network Stratum server; splitting a batch over devices; rank groups. */
+#define BM_MAX_JOB_SUBMITS (1u << 20)
+#define BM_SUBMIT_SHARE 1u   /* hash <= target */
+#define BM_SUBMIT_BLOCK 2u   /* hash <= the target of job->nbits (needs a decodable nbits) */
+#define BM_SUBMIT_INVALID 4u /* extranonce2 >= 2^(8 * extranonce2_size): not hashed */
+typedef struct bm_job_submit {
+    uint64_t extranonce2;
+    uint32_t ntime, nonce;
+    uint32_t version;  /* the full header version field */
+    uint32_t reserved; /* ignored */
+} bm_job_submit_t;     /* 24 bytes */
+typedef struct bm_job_verdict {
+    uint8_t hash[32];  /* most significant byte first; all 0xFF for an INVALID entry */
+    uint32_t status;   /* BM_SUBMIT_* */
+    uint32_t reserved; /* 0 */
+} bm_job_verdict_t;    /* 40 bytes */
+typedef struct bm_job_verify_result {
+    uint64_t n;        /* submissions */
+    uint64_t shares, blocks, invalid; /* verdicts with BM_SUBMIT_SHARE / _BLOCK / _INVALID */
+} bm_job_verify_result_t; /* 32 bytes */
+
+int bm_job_verify_cpu(const bm_job_t* job, const uint8_t target[32], const bm_job_submit_t* submits, size_t n,
+                      bm_job_verdict_t* verdicts, bm_job_verify_result_t* out);
+int bm_job_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const uint8_t target[32], const bm_job_submit_t* submits,
+                      size_t n, bm_job_verdict_t* verdicts, bm_job_verify_result_t* out);
+
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */
 int bm_hash_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,

@@ -98,6 +98,20 @@ inline void target_from_difficulty(double difficulty, uint8_t target[32]) {
     check(bm_target_from_difficulty(difficulty, target), "bm_target_from_difficulty");
 }
 
+// Context::verify_job_submits without a GPU or a context: bm_job_verify_cpu, the
+// specification of the GPU entry (byte-identical verdicts and counts)
+inline bm_job_verify_result_t verify_job_submits_cpu(const Job& job, const uint8_t target[32],
+                                                     const bm_job_submit_t* submits, size_t n,
+                                                     std::vector<bm_job_verdict_t>& verdicts) {
+    if (job.branch.size() % 32 != 0) throw Error(BM_EINVAL, "verify_job_submits_cpu");
+    const bm_job_t j = job.view();
+    bm_job_verify_result_t r;
+    std::vector<bm_job_verdict_t> buf(n);
+    check(bm_job_verify_cpu(&j, target, submits, n, n ? buf.data() : nullptr, &r), "bm_job_verify_cpu");
+    verdicts = std::move(buf);
+    return r;
+}
+
 // Owns a bm_ctx.  Not thread-safe, like the C context (one per OS thread).
 class Context {
    public:
@@ -255,6 +269,20 @@ class Context {
               "bm_search_job_shares_gpu");
         buf.resize(static_cast<size_t>(r.stored));
         shares = std::move(buf);
+        return r;
+    }
+    // a batch of mining.submit tuples of a job against a share target: one verdict
+    // per submission, in the caller's order, into `verdicts` (resized to n), plus
+    // the count of each flag, on the first device: bm_job_verify_gpu
+    bm_job_verify_result_t verify_job_submits(const Job& job, const uint8_t target[32],
+                                              const bm_job_submit_t* submits, size_t n,
+                                              std::vector<bm_job_verdict_t>& verdicts) {
+        if (job.branch.size() % 32 != 0) throw Error(BM_EINVAL, "verify_job_submits");
+        const bm_job_t j = job.view();
+        bm_job_verify_result_t r;
+        std::vector<bm_job_verdict_t> buf(n);
+        check(bm_job_verify_gpu(ctx_, &j, target, submits, n, n ? buf.data() : nullptr, &r), "bm_job_verify_gpu");
+        verdicts = std::move(buf);
         return r;
     }
     // the double SHA-256 of the header under each nonce, 32 bytes each, most

@@ -1,0 +1,28 @@
+"""The share verifier's host code under sanitizers (no GPU): tools/verify_check.cpp,
+a stand-alone program over csrc/bm_job.hpp and csrc/bm_job.cpp, built with ASan
+and UBSan and run on the CPU."""
+import os
+import subprocess
+import tempfile
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "distributed_bitcoin_minter_amd", "csrc")
+
+
+def test_verify_host_code_under_sanitizers():
+    """bm_job_verify_cpu on exactly-sized heap buffers for `submits` and `verdicts`
+    over the edge layouts (extranonce2 against word and block edges, every padding
+    edge, the coinbase limit), INVALID entries, the refusals with canaries, and
+    what the GPU entry's host side prepares (the tail template and extranonce2's
+    three words) replayed against bm_job_header."""
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "verify_check")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
+                               "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                               "-I", CSRC, "-I", os.path.join(ROOT, "include"),
+                               os.path.join(ROOT, "tools", "verify_check.cpp"), os.path.join(CSRC, "bm_job.cpp"),
+                               "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert r.stdout.strip().endswith("verify check ok")
