@@ -1,6 +1,6 @@
 // bm_header.hpp -- Bitcoin block-header search: what the host works out once
 // per call, shared by the launcher (bm_search.cpp), the kernels
-// (bm_header_kernels.hpp) and a stand-alone CPU check (tools/header_precompute_check.cpp).
+// (bm_header_versions_body.inc) and a stand-alone CPU check (tools/header_precompute_check.cpp).
 // Plain C++: no HIP in here.
 //
 // H(n) = SHA256(SHA256(header[0:76] || le32(n))), read as a little-endian
@@ -31,7 +31,9 @@ constexpr int kHeaderTaskBits = 8;  // a task = 2^8 consecutive nonces of one la
                                     // W3's top byte, is the wave-uniform inner counter)
 constexpr uint32_t kHeaderTaskNonces = 1u << kHeaderTaskBits;
 
-// Kernel argument of header_kernel, by value (SGPRs).
+// What header_precompute works out of one header: the per-header terms of the
+// kernels' argument block (HeaderVersionsArgs, bm_header_versions.hpp, holds
+// them per version slot and the schedule terms once).
 struct HeaderArgs {
     uint32_t mid[8];   // state after block 1
     uint32_t a3k, e3k; // round 3 of block 2: a = a3k + W3, e = e3k + W3
@@ -39,12 +41,6 @@ struct HeaderArgs {
     uint32_t w16, w17; // schedule words 16 and 17 of block 2
     uint32_t k18, k19; // W18 = k18 + sigma0(W3), W19 = k19 + W3
     uint32_t k31, k32; // W31 = sigma1(W29) + W24 + k31, W32 = sigma1(W30) + W25 + k32
-    uint32_t tgt[8];   // the target, most significant word first
-    uint32_t lo, hi;   // inclusive nonce range of this launch
-    uint32_t t0;       // first task: task t covers nonces [t << 8, (t << 8) + 255]
-    uint32_t ntask;    // tasks t0 .. t0 + ntask - 1
-    uint32_t chunk_m;  // tasks per lane per dequeued chunk (a chunk = 64 * chunk_m tasks)
-    uint32_t part_off; // first partial slot written by this launch
 };
 
 // Kernel argument of header_hash_kernel.

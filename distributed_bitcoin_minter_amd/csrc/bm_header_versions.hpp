@@ -72,6 +72,12 @@ inline int versions_groups(size_t nver, int cap, uint8_t sizes[BM_MAX_HEADER_VER
     return n;
 }
 
+// The version field of a header as it stands, le32(header[0..3]): the one-entry
+// list under which a search hashes the caller's bytes unchanged.
+inline uint32_t header_version(const uint8_t header[kHeaderBytes]) {
+    return (uint32_t)header[0] | (uint32_t)header[1] << 8 | (uint32_t)header[2] << 16 | (uint32_t)header[3] << 24;
+}
+
 // The caller's header with le32(version) in bytes 0..3.
 inline void header_with_version(const uint8_t header[kHeaderBytes], uint32_t version, uint8_t out[kHeaderBytes]) {
     std::memcpy(out, header, kHeaderBytes);

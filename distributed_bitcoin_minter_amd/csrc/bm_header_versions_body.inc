@@ -1,8 +1,18 @@
 // bm_header_versions_body.inc -- the body of header_versions_kernel<M>
 // (bm_header_versions_inst.hip) and of header_versions_hits_kernel<M>
 // (bm_header_versions_hits_inst.hip), included inside each with
-// BM_VERSIONS_HITS 0 / 1.  Text rather than a function template, for the reason
-// bm_header_body.inc gives: header_versions_kernel compiles to what it always did.
+// BM_VERSIONS_HITS 0 / 1.  The one body of the block-header searches: the
+// single-header calls run it at M = 1.
+//
+// Text rather than a function template: a kernel that hands its by-value
+// argument block on to a function gets the whole block copied at entry, and
+// its register allocation and code object change with that copy.  Included
+// here, header_versions_kernel compiles to what it always did, and the rounds
+// themselves (sha_round, block_round) are functions both modes share anyway.
+//
+// Work distribution as search_body's: each wave dequeues chunks of
+// 64 * chunk_m consecutive tasks from the launch's counter (one returning
+// atomic per chunk, lane 0), lane l taking tasks base + l, base + 64 + l, ...
 //
 // In scope: M, A (HeaderVersionsArgs<M>), part, counter, and
 //   BM_VERSIONS_HITS 0: hit, the device's hit word;
@@ -100,7 +110,7 @@
                     }
                 });
 
-                // ---- per slot: the second hash and the compare of bm_header_body.inc ----
+                // ---- per slot: the second hash (the digest, one block from the IV) and the compare ----
                 static_for<0, M>([&](auto MI) {
                     constexpr int m = decltype(MI)::value;
                     uint32_t d[16];

@@ -1,9 +1,9 @@
 // bm_header_versions_hits_inst.hip -- header_versions_hits_kernel<M>, M = 1, 2, 4:
 // header_versions_kernel<M> in hits mode (bm_header_versions_body.inc with
-// BM_VERSIONS_HITS 1), the kernel of bm_search_header_versions_hits_gpu and its
-// build unit, registered with the launcher (bm_search.cpp) at load time.  A
-// unit of its own, so bm_header_versions_inst.hip's code object holds what it
-// always held.
+// BM_VERSIONS_HITS 1), the kernel of bm_search_header_versions_hits_gpu, of
+// bm_search_header_hits_gpu at M = 1, and its build unit, registered with the
+// launcher (bm_search.cpp) at load time.  A unit of its own, so
+// bm_header_versions_inst.hip's code object holds what it always held.
 //
 // A full scan: every (nonce, version index) pair of the launch's range whose
 // hash meets the target takes the next index of the device's hit counter and,
@@ -12,7 +12,6 @@
 // launches on a device, which may overlap on its streams: the atomicAdd is what
 // keeps their slots distinct.  hit_buf holds hit_cap entries of 16 bytes,
 // 16-byte aligned.
-#define BM_HEADER_PIECES_ONLY 1
 #include "bm_header_kernels.hpp"
 #include "bm_header_versions.hpp"
 

@@ -1,20 +1,19 @@
 // bm_header_versions_inst.hip -- header_versions_kernel<M>, M = 1, 2, 4: the
-// kernel of bm_search_header_versions_gpu and its build unit, registered with
-// the launcher (bm_search.cpp) at load time.  A unit of its own, built from
-// header_kernel's pieces (bm_header_kernels.hpp), so the units of header_kernel
-// and header_hits_kernel hold what they always held.  The body is
+// kernel of bm_search_header_versions_gpu, of bm_search_header_gpu at M = 1,
+// and its build unit, registered with the launcher (bm_search.cpp) at load
+// time.  Built from the pieces of bm_header_kernels.hpp.  The body is
 // bm_header_versions_body.inc, shared with header_versions_hits_kernel<M>
 // (bm_header_versions_hits_inst.hip).
 //
 // A launch scans one nonce range for M versions of one header ("slots";
-// bm_header_versions.hpp).  Per nonce n, with header_kernel's task / inner
-// counter split of W3:
+// bm_header_versions.hpp).  Per nonce n, with the task / inner counter split of
+// W3 that bm_header_kernels.hpp describes:
 //   * rounds 4..63 of block 2 for all M slots in lock-step over ONE schedule
 //     window: each word (sched_word<HeaderBlock2, t>, and the four special
 //     words 18, 19, 31, 32) is computed once and fed to sha_round<t> of every
 //     slot's state.  The schedule costs the same whatever M is;
 //   * then, slot by slot, the 61-round second hash and the hot-path compare
-//     exactly as bm_header_body.inc has them, against one bh for all slots;
+//     (bm_header_kernels.hpp), against one bh for all slots;
 //   * rare path: the exact compare and the range check.  A pair is the key
 //     (n << 32) | version index: a hit does one atomicMin of its key on the
 //     device's hit word, and the running minimum carries the key in the
@@ -27,7 +26,6 @@
 //     smallest hitting nonce is hashed, whatever the timing.  The hit word is
 //     shared by all of a call's launches on the device and set once, before
 //     the first, so a later group scans only up to the best hit so far.
-#define BM_HEADER_PIECES_ONLY 1
 #include "bm_header_kernels.hpp"
 #include "bm_header_versions.hpp"
 

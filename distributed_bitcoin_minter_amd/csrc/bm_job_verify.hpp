@@ -1,6 +1,6 @@
 // bm_job_verify.hpp -- job_verify_kernel, the kernel of bm_job_verify_gpu: one
 // lane per mining.submit tuple of one Stratum job.  Built from sha_compress
-// (bm_kernels.hpp) and le256 (bm_header_kernels.hpp); nothing of header_kernel's
+// (bm_kernels.hpp) and le256 (bm_header_kernels.hpp); nothing of the header search's
 // shortcuts: every lane hashes its own coinbase tail, folds the merkle branch and
 // double-hashes its own header, nb + 1 + 3 * depth + 3 plain compressions.
 //
@@ -26,7 +26,6 @@
 // A lane whose extranonce2 does not fit its field runs along (its words are
 // masked to nothing) and stores the INVALID verdict instead.
 #pragma once
-#define BM_HEADER_PIECES_ONLY 1
 #include "bm_header_kernels.hpp"
 #include "bm_job.hpp"
 

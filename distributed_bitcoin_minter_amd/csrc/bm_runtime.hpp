@@ -114,20 +114,19 @@ struct DeviceCtx {
 // The seven searches share one plan -> enqueue -> combine -> stats path
 // (bm_search.cpp); a Mode says which one a call is, and carries what its
 // kernels take beyond a launch's own arguments.  DESIGN.md section 1, "Host
-// runtime layout", lists what a mode changes.
-enum class Kind { Search, Target, Hits, Header, HeaderHits, HeaderVersions, HeaderVersionsHits };
+// runtime layout", lists what a mode changes.  Five kinds serve the seven: the
+// two single-header searches are HeaderVersions / HeaderVersionsHits over one version.
+enum class Kind { Search, Target, Hits, HeaderVersions, HeaderVersionsHits };
 struct Mode {
     Kind kind = Kind::Search;
-    uint64_t target = 0;  // Target, Hits: the 64-bit bound (Header, HeaderHits: their 256-bit target is in HeaderArgs)
-    uint64_t cap = 0;     // Hits, HeaderHits, HeaderVersionsHits: entries of the hit buffer
+    uint64_t target = 0;  // Target, Hits: the 64-bit bound (the header kinds' 256-bit target is in HeaderVersionsArgs)
+    uint64_t cap = 0;     // Hits, HeaderVersionsHits: entries of the hit buffer
     // first hit wins: launches in ascending nonce order, one hit word per device
     // (HeaderVersions: the word holds a (nonce, version index) key, shared by the device's group launches)
-    bool first_hit() const { return kind == Kind::Target || kind == Kind::Header || kind == Kind::HeaderVersions; }
+    bool first_hit() const { return kind == Kind::Target || kind == Kind::HeaderVersions; }
     // every hit: a counter and a buffer of 16-byte entries per device (d_hcount, d_hbuf)
     // (HeaderVersionsHits: both shared by the device's group launches, the counter zeroed once)
-    bool every_hit() const {
-        return kind == Kind::Hits || kind == Kind::HeaderHits || kind == Kind::HeaderVersionsHits;
-    }
+    bool every_hit() const { return kind == Kind::Hits || kind == Kind::HeaderVersionsHits; }
     // the decimal modes whose kernels take the 64-bit target as a parameter
     bool target64() const { return kind == Kind::Target || kind == Kind::Hits; }
 };
@@ -138,7 +137,6 @@ struct Launch {
     const void* fn;
     union {
         SearchArgs search;  // Search, Target, Hits
-        HeaderArgs header;  // Header, HeaderHits
         HeaderVersionsArgs<kMaxVersionSlots> versions;  // HeaderVersions, HeaderVersionsHits: a launch of M slots reads the first M
     } args;                 // the kernel's first parameter, by value
     uint64_t first_nonce;  // the lowest nonce it scans

@@ -7,10 +7,12 @@
 // combine the devices' partials, read back what an enumeration appended,
 // record the stats.  run_call drives that path for the six searches outside a
 // rank group; what differs between them is a Mode (bm_runtime.hpp), the
-// planner each *_impl passes in (plan_decimal, plan_header, plan_versions, all
-// over plan_devices) and what it alone does with the outcome.  search_impl runs
-// the same stages around its group combine and the balance step.  Plain C++
-// over the HIP host API.
+// planner each *_impl passes in (plan_decimal, plan_versions, both over
+// plan_devices) and what it alone does with the outcome.  bm_search_header_gpu
+// and bm_search_header_hits_gpu are the one-version case of the two
+// version-rolling searches: the same impl over the header's own version field,
+// its answer narrowed.  search_impl runs the same stages around its group
+// combine and the balance step.  Plain C++ over the HIP host API.
 //
 // bm_search_gpu is a drop-in for the reference miner's job loop body
 // (miner.go:58-65): the same (hash, nonce) for the same (msg, range).
@@ -20,7 +22,6 @@
 #include <cstdio>
 #include <cstring>
 
-#include "bm_header_hits.hpp"
 #include "bm_header_versions_hits.hpp"
 #include "bm_job.hpp"
 #include "bm_runtime.hpp"
@@ -41,10 +42,6 @@ const void* g_search[kSearchRows][64];
 // kernel in target / hits mode, every layout
 const void* g_target[2][64];
 const void* g_hits[2][64];
-// header_kernel, filled (with g_header_hash) by bm_header_inst.hip at load time
-const void* g_header_search = nullptr;
-// header_hits_kernel, filled by bm_header_hits_inst.hip at load time
-const void* g_header_hits = nullptr;
 // header_versions_kernel<M> at [M], M = 1, 2, 4, filled by bm_header_versions_inst.hip at load time
 const void* g_header_versions[kMaxVersionSlots + 1];
 // header_versions_hits_kernel<M> at [M], filled by bm_header_versions_hits_inst.hip at load time
@@ -75,12 +72,7 @@ extern "C" void bm_register_hits_kernel(int p, int nbv, const void* fn) {
     if (p >= 0 && p < 64 && nbv >= 1 && nbv <= 2) bm::g_hits[nbv - 1][p] = fn;
 }
 
-extern "C" void bm_register_header_kernels(const void* search_fn, const void* hash_fn) {
-    bm::g_header_search = search_fn;
-    bm::g_header_hash = hash_fn;
-}
-
-extern "C" void bm_register_header_hits_kernel(const void* fn) { bm::g_header_hits = fn; }
+extern "C" void bm_register_header_hash_kernel(const void* fn) { bm::g_header_hash = fn; }
 
 extern "C" void bm_register_header_versions_kernel(int m, const void* fn) {
     if (m >= 1 && m <= bm::kMaxVersionSlots) bm::g_header_versions[m] = fn;
@@ -213,34 +205,17 @@ int size_launch(bm_ctx* ctx, DevicePlan& dp, Kind kind, const bm_segment_t& s) {
     return BM_OK;
 }
 
-// The kernel of a block-header mode that runs m versions in lock-step (m = 1
-// alone for Header and HeaderHits).
-const void* header_kernel_for(Kind kind, int m) {
-    switch (kind) {
-        case Kind::Header: return g_header_search;
-        case Kind::HeaderHits: return g_header_hits;
-        case Kind::HeaderVersions: return g_header_versions[m];
-        case Kind::HeaderVersionsHits: return g_header_versions_hits[m];
-        default: return nullptr;
-    }
-}
-
-HeaderArgs& args_of(Launch& L, const HeaderArgs&) { return L.args.header; }
-HeaderVersionsArgs<kMaxVersionSlots>& args_of(Launch& L, const HeaderVersionsArgs<kMaxVersionSlots>&) {
-    return L.args.versions;
-}
-
 // One device's launch of a block-header kernel: its piece of the nonce range in
-// tasks of 256 nonces, of m hashes each (base: the header's terms, or those of
-// one group of m versions).  Args: HeaderArgs or HeaderVersionsArgs.
-template <class Args>
-int size_header_launch(bm_ctx* ctx, DevicePlan& dp, Kind kind, const Args& base, int m) {
-    const void* fn = header_kernel_for(kind, m);
+// tasks of 256 nonces, of m hashes each (base: the terms of one group of m
+// versions, which the kernel runs in lock-step).
+int size_header_launch(bm_ctx* ctx, DevicePlan& dp, Kind kind, const HeaderVersionsArgs<kMaxVersionSlots>& base,
+                       int m) {
+    const void* fn = (kind == Kind::HeaderVersionsHits ? g_header_versions_hits : g_header_versions)[m];
     if (!fn) return BM_EINTERNAL;
     const uint32_t lo = (uint32_t)dp.piece.lo, hi = (uint32_t)dp.piece.hi;
     Launch L;
     std::memset(&L, 0, sizeof L);
-    Args& A = args_of(L, base);
+    HeaderVersionsArgs<kMaxVersionSlots>& A = L.args.versions;
     A = base;
     A.lo = lo;
     A.hi = hi;
@@ -338,18 +313,7 @@ int plan_decimal(bm_ctx* ctx, const Mode& mode, const uint8_t* msg, size_t len, 
     });
 }
 
-// A block-header search or enumeration (Header, HeaderHits): one launch per device.
-int plan_header(bm_ctx* ctx, const Mode& mode, const uint8_t* header, const uint8_t* target, uint32_t lo,
-                uint32_t hi, std::vector<std::vector<Launch>>& launches) {
-    HeaderArgs base;
-    std::memset(&base, 0, sizeof base);
-    host::header_precompute(header, base);
-    for (int i = 0; i < 8; ++i) base.tgt[i] = host::load_be32(target + 4 * i);
-    return plan_devices(ctx, mode, lo, hi, launches,
-                        [&](DevicePlan& dp) { return size_header_launch(ctx, dp, mode.kind, base, 1); });
-}
-
-// A version-rolling search or enumeration (HeaderVersions, HeaderVersionsHits):
+// A block-header search or enumeration (HeaderVersions, HeaderVersionsHits):
 // every device gets one launch per group of versions over its piece of the
 // nonce range, in group order (they all start at the piece's first nonce, so
 // enqueue_device keeps that order).
@@ -830,85 +794,14 @@ int hits_impl(bm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lower, uint6
     return BM_OK;
 }
 
-// bm_search_header_gpu: the nonce range cut over the devices by the
-// partitioner, one launch and one hit word per device; the host takes the
-// lowest-nonce hit, or else the lexicographic min of the (top 64 bits, nonce)
-// partials, and recomputes the full 256-bit hash of the one nonce it returns.
-int header_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, const uint8_t* target,
-                bm_header_result_t* out) {
-    const Mode mode{Kind::Header};
-    std::memset(out->hash, 0xFF, sizeof out->hash);
-    out->nonce = 0xFFFFFFFFu;
-    out->found = 0;
-    Call c;
-    const int rc = run_call(ctx, mode, lo > hi, c, [&](auto& launches) {
-        return plan_header(ctx, mode, header, target, lo, hi, launches);
-    });
-    if (rc != BM_OK || c.empty) return rc;
-
-    const uint64_t hit = scan_hit_words(ctx, c.launches);
-    const bool found = hit != UINT64_MAX;
-    const uint64_t n = found ? hit : c.best.nonce;
-    if (n > 0xFFFFFFFFull) return fail_call(ctx, BM_EINTERNAL);  // a non-empty range always has a minimum
-    bm_header_result_t r;
-    host::header_hash_msb(header, (uint32_t)n, r.hash);
-    r.nonce = (uint32_t)n;
-    r.found = found ? 1 : 0;
-    // the device's claim against the host's hash of that nonce
-    const bool meets = std::memcmp(r.hash, target, 32) <= 0;
-    if (found ? !meets : (meets || host::hash_top64(r.hash) != c.best.hash)) return fail_call(ctx, BM_EINTERNAL);
-    *out = r;
-    return BM_OK;
-}
-
-// bm_search_header_hits_gpu: a full scan, one launch of header_hits_kernel per
-// device over the partitioner's pieces.  Each device appends {top 64 bits, nonce}
-// to d_hbuf through d_hcount (what bm_search_hits_gpu uses, with the same
-// 16-byte entries); the host reads every counter back and, only when their sum
-// fits in cap, the entries, which header_hits_collect sorts, rehashes in full
-// and checks.  The best share is header_impl's found = 0 answer.  hits and out
-// are written last, on success only.
-int header_hits_impl(bm_ctx* ctx, const uint8_t* header, uint32_t lo, uint32_t hi, const uint8_t* target,
-                     bm_header_hit_t* hits, size_t cap, bm_header_hits_result_t* out) {
-    const Mode mode{Kind::HeaderHits, 0, (uint64_t)cap};
-    bm_header_hits_result_t r;
-    std::memset(&r, 0, sizeof r);
-    std::memset(r.hash, 0xFF, sizeof r.hash);
-    r.nonce = 0xFFFFFFFFu;
-    *out = r;
-    std::vector<bm_header_hit_t> list;
-    Call c;
-    const int rc = run_call(ctx, mode, lo > hi, c, [&](auto& launches) {
-        return plan_header(ctx, mode, header, target, lo, hi, launches);
-    }, 1 /* a nonce counts once */, [&]() -> int {
-        list.resize(c.entries.size());
-        if (!list.empty())
-            BM_TRY(host::header_hits_collect(header, target, lo, hi, c.entries.data(), c.counts.data(),
-                                             (int)c.counts.size(), list.data()));
-        // the best share: the device's claim against the host's hash of that nonce
-        if (c.best.nonce > 0xFFFFFFFFull) return BM_EINTERNAL;  // a non-empty range always has a minimum
-        host::header_hash_msb(header, (uint32_t)c.best.nonce, r.hash);
-        r.nonce = (uint32_t)c.best.nonce;
-        if (host::hash_top64(r.hash) != c.best.hash) return BM_EINTERNAL;
-        // ... and against the count: a best share at or below the target is itself a hit
-        if (c.count == 0 && std::memcmp(r.hash, target, 32) <= 0) return BM_EINTERNAL;
-        return BM_OK;
-    });
-    if (rc != BM_OK || c.empty) return rc;
-
-    r.count = c.count;
-    r.stored = list.size();
-    if (r.stored) std::memcpy(hits, list.data(), list.size() * sizeof(bm_header_hit_t));
-    *out = r;
-    return BM_OK;
-}
-
-// bm_search_header_versions_gpu: header_impl for several version fields.  Every
-// device scans its piece of the nonce range once per group of versions; its
+// bm_search_header_versions_gpu, and bm_search_header_gpu with the header's own
+// version as the whole list: the nonce range cut over the devices by the
+// partitioner.  Every device scans its piece once per group of versions; its
 // hit word holds the smallest (nonce, version index) key of all its launches.
 // The host takes the lowest device's hit (pieces ascend with the device
-// index), or else the minimum of the (top 64 bits, key) partials, and checks
-// it (header_versions_select).
+// index), or else the minimum of the (top 64 bits, key) partials, recomputes
+// the full 256-bit hash of the one pair it returns and checks the device's
+// claim against it (header_versions_select).
 int header_versions_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* versions, size_t nver, uint32_t lo,
                          uint32_t hi, const uint8_t* target, bm_header_versions_result_t* out) {
     const Mode mode{Kind::HeaderVersions};
@@ -930,18 +823,22 @@ int header_versions_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* ver
     return BM_OK;
 }
 
-// bm_search_header_versions_hits_gpu: header_versions_impl's launches (one per
-// device and group of versions, over the partitioner's pieces) in hits mode,
-// with header_hits_impl's host side.  All of a device's launches append
-// {top 64 bits, (nonce << 32) | version index} to d_hbuf through d_hcount,
-// zeroed once before the device's first launch; the host reads every counter
-// back and, only when their sum fits in cap, the entries, which
-// header_versions_hits_collect sorts by (nonce, index), rehashes in full and
-// checks.  The best share is header_versions_impl's found = 0 answer.  hits
-// and out are written last, on success only.
+// bm_search_header_versions_hits_gpu, and bm_search_header_hits_gpu with the
+// header's own version as the whole list (Hit: the caller's entry type,
+// bm_header_version_hit_t or bm_header_hit_t): a full scan over
+// header_versions_impl's launches (one per device and group of versions, over
+// the partitioner's pieces) in hits mode.  All of a device's launches append
+// {top 64 bits, (nonce << 32) | version index} to d_hbuf through d_hcount (what
+// bm_search_hits_gpu uses, with the same 16-byte entries), zeroed once before
+// the device's first launch; the host reads every counter back and, only when
+// their sum fits in cap, the entries, which header_versions_hits_collect sorts
+// by (nonce, index), rehashes in full and checks.  The best share is
+// header_versions_impl's found = 0 answer.  hits and out are written last, on
+// success only.
+template <class Hit>
 int header_versions_hits_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t* versions, size_t nver,
-                              uint32_t lo, uint32_t hi, const uint8_t* target, bm_header_version_hit_t* hits,
-                              size_t cap, bm_header_versions_hits_result_t* out) {
+                              uint32_t lo, uint32_t hi, const uint8_t* target, Hit* hits, size_t cap,
+                              bm_header_versions_hits_result_t* out) {
     const Mode mode{Kind::HeaderVersionsHits, 0, (uint64_t)cap};
     bm_header_versions_hits_result_t r;
     std::memset(&r, 0, sizeof r);
@@ -949,7 +846,7 @@ int header_versions_hits_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t
     r.nonce = 0xFFFFFFFFu;
     r.version = versions[0];
     *out = r;
-    std::vector<bm_header_version_hit_t> list;
+    std::vector<Hit> list;
     Call c;
     const int rc = run_call(ctx, mode, lo > hi, c, [&](auto& launches) {
         return plan_versions(ctx, mode, header, versions, nver, target, lo, hi, launches);
@@ -965,7 +862,7 @@ int header_versions_hits_impl(bm_ctx* ctx, const uint8_t* header, const uint32_t
 
     r.count = c.count;
     r.stored = list.size();
-    if (r.stored) std::memcpy(hits, list.data(), list.size() * sizeof(bm_header_version_hit_t));
+    if (r.stored) std::memcpy(hits, list.data(), list.size() * sizeof(Hit));
     *out = r;
     return BM_OK;
 }
@@ -985,12 +882,12 @@ int job_shares_impl(bm_ctx* ctx, const bm_job_t* job, uint32_t ntime, uint64_t e
     host::JobMerge merge(cap, has_block ? block : nullptr, ntime, en2_lo, versions[0]);
     bm_header_versions_hits_result_t r;
     uint8_t header[kHeaderBytes] = {};
+    std::unique_ptr<bm_header_version_hit_t[]> hits;  // one header's list: at most cap entries
     if (en2_lo > en2_hi || lo > hi) {
-        BM_TRY(header_versions_hits_impl(ctx, header, versions, nver, 1, 0, target, nullptr, 0, &r));
+        BM_TRY(header_versions_hits_impl(ctx, header, versions, nver, 1, 0, target, hits.get(), 0, &r));
         merge.finish(shares, out);
         return BM_OK;
     }
-    std::unique_ptr<bm_header_version_hit_t[]> hits;  // one header's list: at most cap entries
     if (cap > 0) hits.reset(new bm_header_version_hit_t[cap]);
     for (uint64_t e = en2_lo;; ++e) {  // ends on e == en2_hi: en2_hi + 1 may wrap
         host::job_header(job, e, ntime, versions[0], header);
@@ -1048,8 +945,14 @@ int bm_search_header_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t nonce_lo
                          const uint8_t* target, bm_header_result_t* out) {
     if (!ctx || !header || !target || !out) return BM_EINVAL;
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    const uint32_t version = bm::host::header_version(header);  // the one-version case: the header as it stands
     return bm::call_into(out, [&](bm_header_result_t* r) {
-        return bm::header_impl(ctx, header, nonce_lo, nonce_hi, target, r);
+        bm_header_versions_result_t v;
+        BM_TRY(bm::header_versions_impl(ctx, header, &version, 1, nonce_lo, nonce_hi, target, &v));
+        std::memcpy(r->hash, v.hash, sizeof r->hash);
+        r->nonce = v.nonce;
+        r->found = v.found;
+        return BM_OK;
     });
 }
 
@@ -1059,8 +962,16 @@ int bm_search_header_hits_gpu(bm_ctx_t* ctx, const uint8_t* header, uint32_t non
     if (!ctx || !header || !target || !out) return BM_EINVAL;
     if (cap > BM_MAX_HEADER_HITS || (!hits && cap > 0)) return BM_EINVAL;
     if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    const uint32_t version = bm::host::header_version(header);  // the one-version case: the header as it stands
     return bm::call_into(out, [&](bm_header_hits_result_t* r) {
-        return bm::header_hits_impl(ctx, header, nonce_lo, nonce_hi, target, hits, cap, r);
+        bm_header_versions_hits_result_t v;
+        BM_TRY(bm::header_versions_hits_impl(ctx, header, &version, 1, nonce_lo, nonce_hi, target, hits, cap, &v));
+        std::memcpy(r->hash, v.hash, sizeof r->hash);
+        r->nonce = v.nonce;
+        r->reserved = 0;
+        r->count = v.count;
+        r->stored = v.stored;
+        return BM_OK;
     });
 }
 

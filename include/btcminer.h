@@ -255,7 +255,7 @@ int bm_search_hits_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, uint64_t l
  * context with world > 1 returns BM_EINVAL.
  * bm_ctx_set_balance does not learn from these calls; bm_ctx_set_test_fault
  * applies as for a search; bm_ctx_last_stats is filled, one launch per device
- * (p = digits = inner_digits = 0: a launch of header_kernel);
+ * (p = digits = inner_digits = 0: a launch of the header kernel);
  * bm_ctx_last_target_stats is filled with the nonces dispatched, as for a
  * target search.
  *
@@ -316,7 +316,7 @@ int bm_header_target_from_bits(uint32_t nbits, uint8_t target[32]);
  * by host copies.  A rank context with world > 1 returns BM_EINVAL.
  * bm_ctx_set_balance does not learn from these calls; bm_ctx_set_test_fault
  * applies as for a header search; bm_ctx_last_stats is filled, one launch per
- * device (a launch of header_hits_kernel; nonces = the range size);
+ * device (a launch of the header kernel in hits mode; nonces = the range size);
  * bm_ctx_last_target_stats is not touched.
  * Cost: that of a full bm_search_header_gpu scan while hits are rare.  Every
  * hit is one atomic on one word per device and, when stored, one sha256d on

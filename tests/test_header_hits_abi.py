@@ -1,10 +1,8 @@
 """The block-header share enumeration's C ABI and ctypes mirrors (no GPU):
 bm_search_header_hits_gpu is additive, so the ABI version stays 7."""
 import ctypes
-import glob
 import os
 import subprocess
-import sys
 import tempfile
 
 import pytest
@@ -13,13 +11,11 @@ from conftest import ROOT
 import distributed_bitcoin_minter_amd as pkg
 from distributed_bitcoin_minter_amd import _lib
 
-BUILD = os.path.join(ROOT, "distributed_bitcoin_minter_amd", "csrc", "build")
-
 
 def test_symbols_exported():
     lib = _lib.load()
     assert lib.bm_abi_version() == _lib.BM_ABI_VERSION == 7
-    for name in ("bm_search_header_hits_gpu", "bm_register_header_hits_kernel"):
+    for name in ("bm_search_header_hits_gpu",):
         assert hasattr(lib, name), name
     assert pkg.HeaderHit is _lib.HeaderHit and pkg.HeaderHitsResult is _lib.HeaderHitsResult
     assert {"HeaderHit", "HeaderHitsResult"} <= set(pkg.__all__)
@@ -88,44 +84,17 @@ def test_python_argument_checks():
 
 
 def test_collect_under_sanitizers():
-    """host::header_hits_collect in a stand-alone program of its own
-    (tools/header_hits_check.cpp), built with ASan and UBSan and run on the CPU."""
+    """host::header_versions_hits_collect with bm_header_hit_t output over one
+    version, the host half of this call, in a stand-alone program
+    (tools/header_versions_hits_check.cpp, its one-version cases), built with
+    ASan and UBSan and run on the CPU."""
     with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "header_hits_check")
+        exe = os.path.join(d, "header_versions_hits_check")
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
                                "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                                "-I", os.path.join(ROOT, "distributed_bitcoin_minter_amd", "csrc"),
                                "-I", os.path.join(ROOT, "include"),
-                               os.path.join(ROOT, "tools", "header_hits_check.cpp"), "-o", exe])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+                               os.path.join(ROOT, "tools", "header_versions_hits_check.cpp"), "-o", exe])
+        r = subprocess.run([exe, "--one-version"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.stdout.strip().endswith("header hits check ok")
-
-
-def _rows(*flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_inner.py"), BUILD, *flags, "-v"],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout[-2000:]
-    return r.stdout
-
-
-def test_header_hits_kernel_inner_loop_is_register_only():
-    """header_hits_kernel's per-nonce block in the built device assembly holds
-    no scratch or memory operation, and costs what header_kernel's does
-    (tools/check_inner.py --header-hits)."""
-    if not (glob.glob(os.path.join(BUILD, "bm_header_hits_inst-hip-amdgcn-amd-amdhsa-gfx950.s")) and
-            glob.glob(os.path.join(BUILD, "bm_header_inst-hip-amdgcn-amd-amdhsa-gfx950.s"))):
-        pytest.skip("device assembly not built (make -C distributed_bitcoin_minter_amd/csrc)")
-    out = _rows("--header-hits")
-    assert "1 kernels checked, 0 with scratch" in out, out[-500:]
-    row = next(ln for ln in out.splitlines() if ":hdrh" in ln)
-    assert "mem=0" in row, row
-    hits_valu = int(row.split("VALU=")[1].split()[0])
-    hdr = next(ln for ln in _rows("--header").splitlines() if ":hdr " in ln)
-    hdr_valu = int(hdr.split("VALU=")[1].split()[0])
-    print(row, hdr, sep="\n")
-    assert abs(hits_valu - hdr_valu) <= 0.01 * hdr_valu, (row, hdr)
-    # no scratch anywhere in the kernel
-    with open(os.path.join(BUILD, "bm_header_hits_inst.res")) as f:
-        res = f.read()
-    assert "header_hits_kernel" in res and "ScratchSize [bytes/lane]: 0" in res, res[-1500:]

@@ -196,18 +196,21 @@ def _field(row, key):
 def test_hits_kernels_inner_loop_is_register_only():
     """The built header_versions_hits_kernel<M>: no scratch or memory operation
     in the per-nonce code, and for M = 2 and 4 the shared schedule still shows:
-    fewer VALU ops and fewer issue slots per hash than header_kernel in the same
-    build, as for header_versions_kernel<M> (tools/check_inner.py
-    --header-versions-hits)."""
+    fewer VALU ops and fewer issue slots per hash than header_versions_kernel<1>
+    (the first-hit kernel of one version) in the same build, as for
+    header_versions_kernel<M>; at M = 1 the hits mode costs what the first-hit
+    mode does, within 1% (tools/check_inner.py --header-versions-hits)."""
     if not (glob.glob(os.path.join(BUILD, "bm_header_versions_hits_inst-hip-amdgcn-amd-amdhsa-gfx950.s")) and
             glob.glob(os.path.join(BUILD, "bm_header_versions_inst-hip-amdgcn-amd-amdhsa-gfx950.s"))):
         pytest.skip("device assembly not built (make -C distributed_bitcoin_minter_amd/csrc)")
     out = _rows("--header-versions-hits")
     assert "3 kernels checked, 0 with scratch" in out, out[-500:]
-    hdr = next(ln for ln in _rows("--header").splitlines() if ":hdr " in ln)
+    hdr = next(ln for ln in _rows("--header-versions").splitlines() if ":hdrv1 " in ln)
     hdr_valu = _field(hdr, "VALU")
-    hdr_slots = max(_field(hdr, "slow"), hdr_valu / 2)  # DESIGN.md section 5: max(slow, (slow + fast) / 2)
+    hdr_slots = _field(hdr, "slots/hash")  # DESIGN.md section 5: max(slow, (slow + fast) / 2)
     print(hdr)
+    hits1 = next(ln for ln in out.splitlines() if ":hdrvh1 " in ln)
+    assert abs(_field(hits1, "VALU") - hdr_valu) <= 0.01 * hdr_valu, (hits1, hdr)
     for m in (1, 2, 4):
         row = next(ln for ln in out.splitlines() if f":hdrvh{m} " in ln)
         print(row)

@@ -42,7 +42,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--ops", type=int, default=None, help="VALU ops per nonce of header_kernel's inner loop")
+    ap.add_argument("--ops", type=int, default=None, help="VALU ops per nonce of the header kernel's inner loop (check_inner.py row hdrv1)")
     ap.add_argument("--lib", action="append", default=[], help="another build of the library to alternate with")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Measure bm_search_header_hits_gpu on one GPU (DESIGN.md section 4,
-"header_hits_kernel"): medians of --rounds rounds after --warmup, the variants
+"Block-header share enumeration"): medians of --rounds rounds after --warmup, the variants
 of a comparison alternating inside each round (their order reversed every
 second round), in one process.
 
@@ -14,11 +14,13 @@ second round), in one process.
               called from hit to hit (--walk-bits: over [0, 2^B-1], once)
   back2back   four consecutive calls over [0, 2^32-1] with ntime rolled against
               four times the single call's median
-  parent      (--parent-lib) bm_search_header_gpu and bm_search_gpu (C2) of this
+  parent      (--parent-lib) bm_search_header_gpu, bm_search_gpu (C2) and
+              bm_search_header_hits_gpu (32, 24, 16, 12 zero bits) of this
               tree's library against another build's, alternating
 
 Writes profiles/header_hits/bench_header_hits.json and README.md (and
-ab_parent.log with --parent-lib)."""
+ab_parent.log with --parent-lib; --only-parent: ab_parent.log and
+ab_parent.json alone)."""
 import argparse
 import ctypes
 import json
@@ -36,6 +38,7 @@ GENESIS = bytes.fromhex("0100000000000000000000000000000000000000000000000000000
                         "67768f617fc81bc3888a51323a9fb8aa4b1e5e4a29ab5f49ffff001d1dac2b7c")
 U32 = (1 << 32) - 1
 OUT = os.path.join(ROOT, "profiles", "header_hits")
+HITS_AB_BITS = (32, 24, 16, 12)  # the parent A/B of bm_search_header_hits_gpu: zero bits of its targets
 
 
 def zero_bits(z):
@@ -86,7 +89,10 @@ class RawLib:
                                       P(_lib.Result)]
         lib.bm_search_header_gpu.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p,
                                              P(_lib.HeaderResult)]
+        lib.bm_search_header_hits_gpu.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p,
+                                                  P(_lib.HeaderHit), ctypes.c_size_t, P(_lib.HeaderHitsResult)]
         self.lib, self.h = lib, vp()
+        self.buf = (_lib.HeaderHit * _lib.BM_MAX_HEADER_HITS)()
         _lib.check(lib.bm_ctx_create(1, ctypes.byref(self.h)), "bm_ctx_create")
 
     def search(self, msg, lo, hi):
@@ -99,6 +105,14 @@ class RawLib:
         _lib.check(self.lib.bm_search_header_gpu(self.h, header, lo, hi, target.to_bytes(32, "big"), ctypes.byref(r)),
                    "bm_search_header_gpu")
         return bool(r.found), int.from_bytes(bytes(r.hash), "big"), r.nonce
+
+    def hits(self, header, lo, hi, target):
+        """(count, stored, best share, the first and the last entry)."""
+        r = _lib.HeaderHitsResult()
+        _lib.check(self.lib.bm_search_header_hits_gpu(self.h, header, lo, hi, target.to_bytes(32, "big"), self.buf,
+                                                      len(self.buf), ctypes.byref(r)), "bm_search_header_hits_gpu")
+        ends = [(bytes(self.buf[i].hash), self.buf[i].nonce) for i in ((0, r.stored - 1) if r.stored else ())]
+        return r.count, r.stored, (int.from_bytes(bytes(r.hash), "big"), r.nonce), ends
 
     def close(self):
         self.lib.bm_ctx_destroy(self.h)
@@ -119,12 +133,27 @@ def parent_ab(a, ctx, header0, res):
         assert last["header_new"] == last["header_parent"] and last["c2_new"] == last["c2_parent"]
         res["parent"] = dict(summary(ms), ratio_header=ratios(ms, "header_new", "header_parent"),
                              ratio_c2=ratios(ms, "c2_new", "c2_parent"))
+        # bm_search_header_hits_gpu, both libraries through the same plain ctypes
+        # path: the sparse full scans, and the entry path over the density rows' ranges
+        new = RawLib(os.path.join(ROOT, "distributed_bitcoin_minter_amd", "libbtcminer.so"))
+        try:
+            for z in HITS_AB_BITS:
+                hi = min(U32, (1 << (19 + z)) - 1)
+                ms, last = alternate({"new": lambda: new.hits(GENESIS, 0, hi, zero_bits(z)),
+                                      "parent": lambda: old.hits(GENESIS, 0, hi, zero_bits(z))}, a.rounds, a.warmup)
+                assert last["new"] == last["parent"], z
+                s = summary(ms)
+                res["parent"].update({f"hits_{z}_new": s["new"], f"hits_{z}_parent": s["parent"],
+                                      f"ratio_hits_{z}": ratios(ms, "new", "parent"),
+                                      f"hits_{z}_range": [0, hi], f"hits_{z}_count": last["new"][0]})
+        finally:
+            new.close()
     finally:
         old.close()
     with open(os.path.join(a.out, "ab_parent.log"), "w") as f:
         f.write("this tree's library against the parent commit's, alternating in one process, "
                 f"{a.rounds} rounds after {a.warmup} warm-up; per-round new / parent\n")
-        for k in ("header", "c2"):
+        for k in ("header", "c2") + tuple(f"hits_{z}" for z in HITS_AB_BITS):
             r = res["parent"]["ratio_" + k]
             f.write(f"{k}: new {res['parent'][k + '_new']['median_ms']:.2f} ms, parent "
                     f"{res['parent'][k + '_parent']['median_ms']:.2f} ms, ratio median {r['median']:.4f} "
@@ -133,6 +162,10 @@ def parent_ab(a, ctx, header0, res):
         f.write(f"control (search_header against itself): ratio median {c['median']:.4f} "
                 f"[{c['min']:.4f}, {c['max']:.4f}]\n")
     print("parent", json.dumps(res["parent"]), flush=True)
+    if a.only_parent:
+        with open(os.path.join(a.out, "ab_parent.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     return 0
 
 
@@ -239,7 +272,7 @@ def main():
         json.dump(res, f, indent=1)
         f.write("\n")
     c = res["control"]["ratio"]
-    lines = ["# header_hits_kernel on one MI355X", "",
+    lines = ["# bm_search_header_hits_gpu on one MI355X", "",
              f"`tools/bench_header_hits.py`: medians of {a.rounds} rounds after {a.warmup} warm-up, the variants of a "
              "comparison alternating in one process.  Raw figures: `bench_header_hits.json`.", "",
              f"* control, `search_header` at target 0 against itself over 2^32 nonces: "
