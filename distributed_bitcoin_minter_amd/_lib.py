@@ -173,9 +173,56 @@ class JobVerdict(ctypes.Structure):
     def is_invalid(self) -> bool:
         return bool(self.status & BM_SUBMIT_INVALID)
 
+    @property
+    def is_ntime(self) -> bool:
+        """ntime outside the window (Context.verify_pool_submits only)."""
+        return bool(self.status & 8)  # BM_SUBMIT_NTIME
+
 
 class JobVerifyResult(ctypes.Structure):
     _fields_ = [("n", c_u64), ("shares", c_u64), ("blocks", c_u64), ("invalid", c_u64)]
+
+
+BM_MAX_POOL_SESSIONS = 1 << 20
+BM_SUBMIT_NTIME = 8
+
+
+class PoolSessionStruct(ctypes.Structure):
+    """bm_pool_session_t: the first extranonce1_len bytes of extranonce1 count;
+    target most significant byte first."""
+    _fields_ = [("extranonce1", ctypes.c_uint8 * 8), ("target", ctypes.c_uint8 * 32)]
+
+
+class PoolSession:
+    """One connection of a pool: its extranonce1 (1..8 bytes, the size the job
+    states) and its share target as an integer."""
+    __slots__ = ("extranonce1", "target")
+
+    def __init__(self, extranonce1: bytes, target: int):
+        if not isinstance(extranonce1, (bytes, bytearray)) or not 1 <= len(extranonce1) <= 8:
+            raise ValueError(f"extranonce1 must be 1..8 bytes, got {extranonce1!r}")
+        if not isinstance(target, int) or isinstance(target, bool) or not 0 <= target < 1 << 256:
+            raise ValueError("target must be in 0..2^256-1")
+        self.extranonce1, self.target = bytes(extranonce1), target
+
+    def __repr__(self):
+        return f"PoolSession({self.extranonce1!r}, {self.target:#x})"
+
+    def __eq__(self, other):
+        return isinstance(other, PoolSession) and (self.extranonce1, self.target) == (other.extranonce1, other.target)
+
+    def __hash__(self):
+        return hash((self.extranonce1, self.target))
+
+
+class PoolSubmit(ctypes.Structure):
+    """bm_pool_submit_t: bm_job_submit_t with the session index where that one
+    has `reserved`; version is the full header version field."""
+    _fields_ = [("extranonce2", c_u64), ("ntime", c_u32), ("nonce", c_u32), ("version", c_u32), ("session", c_u32)]
+
+
+class PoolVerifyResult(ctypes.Structure):
+    _fields_ = [("n", c_u64), ("shares", c_u64), ("blocks", c_u64), ("invalid", c_u64), ("ntime", c_u64)]
 
 
 class Segment(ctypes.Structure):
@@ -272,6 +319,10 @@ def _open(path):
                                P(JobVerifyResult)], ctypes.c_int),
         "bm_job_verify_gpu": ([vp, P(JobStruct), ctypes.c_char_p, P(JobSubmit), ctypes.c_size_t, P(JobVerdict),
                                P(JobVerifyResult)], ctypes.c_int),
+        "bm_pool_verify_cpu": ([P(JobStruct), P(PoolSessionStruct), ctypes.c_size_t, P(PoolSubmit), ctypes.c_size_t,
+                                c_u32, c_u32, P(JobVerdict), P(PoolVerifyResult)], ctypes.c_int),
+        "bm_pool_verify_gpu": ([vp, P(JobStruct), P(PoolSessionStruct), ctypes.c_size_t, P(PoolSubmit),
+                                ctypes.c_size_t, c_u32, c_u32, P(JobVerdict), P(PoolVerifyResult)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -576,6 +627,83 @@ def verify_submits_cpu(job, submits, target):
     return _verify(load().bm_job_verify_cpu, "bm_job_verify_cpu", job, submits, target)
 
 
+def parse_pool_submit(params, job, sessions_by_worker, mask: int = BIP320_MASK):
+    """parse_submit for a pool: params[0], the worker's name, is resolved to its
+    session index through sessions_by_worker (a mapping name -> index), which
+    the result carries as "session" beside parse_submit's fields.  Raises
+    parse_submit's reasons, and ValueError("worker: ...") for a name the mapping
+    does not hold."""
+    sub = parse_submit(params, job, mask)
+    worker = params[0]
+    if not isinstance(worker, str) or worker not in sessions_by_worker:
+        raise ValueError(f"worker: no session for {worker!r}")
+    return dict(sub, session=sessions_by_worker[worker])
+
+
+def _session_array(sessions, size):
+    """A (PoolSessionStruct * n) array from one (used as it is) or from an
+    iterable of PoolSession or (extranonce1, target) pairs, each extranonce1 of
+    size bytes."""
+    if isinstance(sessions, ctypes.Array) and sessions._type_ is PoolSessionStruct:
+        return sessions
+    rows = [s if isinstance(s, PoolSession) else PoolSession(*s) for s in sessions]
+    arr = (PoolSessionStruct * len(rows))()
+    for a, s in zip(arr, rows):
+        if len(s.extranonce1) != size:
+            raise ValueError(f"every session's extranonce1 is {size} bytes (the job's), got {s.extranonce1!r}")
+        ctypes.memmove(a.extranonce1, s.extranonce1, size)
+        ctypes.memmove(a.target, s.target.to_bytes(32, "big"), 32)
+    return arr
+
+
+def _pool_submit_array(submits):
+    """A (PoolSubmit * n) array from one (used as it is) or from an iterable of
+    dicts (extranonce2, ntime, nonce, version, session: parse_pool_submit's) or
+    (extranonce2, ntime, nonce, version, session) tuples."""
+    if isinstance(submits, ctypes.Array) and submits._type_ is PoolSubmit:
+        return submits
+    keys = ("extranonce2", "ntime", "nonce", "version", "session")
+    rows = []
+    for s in submits:
+        row = tuple(s[k] for k in keys) if isinstance(s, dict) else tuple(s)
+        if len(row) != 5:
+            raise ValueError(f"a pool submission is (extranonce2, ntime, nonce, version, session), got {s!r}")
+        if not isinstance(row[0], int) or isinstance(row[0], bool) or not 0 <= row[0] <= U64_MAX:
+            raise ValueError(f"extranonce2 must be in 0..2^64-1, got {row[0]!r}")
+        for v, what in zip(row[1:], keys[1:]):
+            _u32(v, what)
+        rows.append(row)
+    arr = (PoolSubmit * len(rows))()
+    for a, row in zip(arr, rows):
+        a.extranonce2, a.ntime, a.nonce, a.version, a.session = row
+    return arr
+
+
+def _pool_verify(call, what, job, sessions, submits, ntime_lo, ntime_hi):
+    if not isinstance(job, Job):
+        raise ValueError("job must be a Job")
+    if not 1 <= len(job.extranonce1) <= 8:
+        raise ValueError(f"the job's extranonce1 gives the size of every session's: 1..8 bytes, got {len(job.extranonce1)}")
+    ses = _session_array(sessions, len(job.extranonce1))
+    arr = _pool_submit_array(submits)
+    if len(arr) > BM_MAX_JOB_SUBMITS:
+        raise ValueError(f"at most {BM_MAX_JOB_SUBMITS} submissions per call, got {len(arr)}")
+    if len(ses) > BM_MAX_POOL_SESSIONS:
+        raise ValueError(f"at most {BM_MAX_POOL_SESSIONS} sessions per call, got {len(ses)}")
+    _u32(ntime_lo, "ntime_lo"), _u32(ntime_hi, "ntime_hi")
+    verdicts = (JobVerdict * len(arr))()
+    r = PoolVerifyResult()
+    check(call(ctypes.byref(job.struct), ses if len(ses) else None, len(ses), arr if len(arr) else None, len(arr),
+               ntime_lo, ntime_hi, verdicts if len(arr) else None, ctypes.byref(r)), what)
+    return verdicts, r
+
+
+def verify_pool_submits_cpu(job, sessions, submits, ntime_lo: int = 0, ntime_hi: int = (1 << 32) - 1):
+    """Context.verify_pool_submits without a GPU or a context (bm_pool_verify_cpu,
+    pure CPU): the specification of the GPU entry, byte-identical to it."""
+    return _pool_verify(load().bm_pool_verify_cpu, "bm_pool_verify_cpu", job, sessions, submits, ntime_lo, ntime_hi)
+
+
 def _header_bytes(header) -> bytes:
     header = bytes(header)
     if len(header) != HEADER_BYTES:
@@ -870,6 +998,20 @@ class Context:
         JobVerifyResult with n and the count of each flag."""
         return _verify(lambda *a: self._lib.bm_job_verify_gpu(self.handle, *a), "bm_job_verify_gpu", job, submits,
                        target)
+
+    def verify_pool_submits(self, job, sessions, submits, ntime_lo: int = 0, ntime_hi: int = U32_MAX):
+        """One job's submissions from many sessions in one call, one GPU lane per
+        submission (bm_pool_verify_gpu) -> (verdicts, result).  sessions: an
+        iterable of PoolSession (or (extranonce1, target) pairs), each
+        extranonce1 as long as job.extranonce1, whose bytes are not used
+        otherwise; submits: a (PoolSubmit * n) array, or an iterable of dicts
+        with extranonce2, ntime, nonce, version and session (parse_pool_submit's
+        answer) or of such 5-tuples.  A verdict is verify_submits' with is_share
+        against the session's own target, is_ntime for an ntime outside
+        [ntime_lo, ntime_hi] (hashed all the same), and is_invalid also for a
+        session index past the table; result is a PoolVerifyResult."""
+        return _pool_verify(lambda *a: self._lib.bm_pool_verify_gpu(self.handle, *a), "bm_pool_verify_gpu", job,
+                            sessions, submits, ntime_lo, ntime_hi)
 
     def search_header_hits(self, header: bytes, nonce_lo: int = 0, nonce_hi: int = U32_MAX, target=U256_MAX,
                            cap: int = 4096):

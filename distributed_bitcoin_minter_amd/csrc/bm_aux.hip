@@ -1,8 +1,9 @@
 // bm_aux.hip -- the one unit of the host runtime with device code: the small
 // kernels of bm_aux_kernels.hpp, the host wrapper the searches launch the
 // second-pass reduction through, and the entry points outside the search
-// path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu, and bm_job_verify_gpu,
-// whose kernel has a unit of its own, bm_job_verify_inst.hip).  See
+// path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu, and bm_job_verify_gpu
+// and bm_pool_verify_gpu, whose kernels have units of their own,
+// bm_job_verify_inst.hip and bm_pool_verify_inst.hip).  See
 // bm_runtime.hpp for the layout of the host runtime.
 #include <hip/hip_runtime.h>
 
@@ -180,10 +181,95 @@ int job_verify_impl(bm_ctx* ctx, const bm_job_t* job, const uint8_t* target, con
     return BM_OK;
 }
 
+// pool_verify_kernel, registered by bm_pool_verify_inst.hip at load time
+const void* g_pool_verify = nullptr;
+
+// bm_pool_verify_gpu on the first device, the shape of job_verify_impl: the job's
+// tail template, its branch, the session table and the submissions go up in one
+// copy, one launch gives a lane to each submission, the verdicts come back in one
+// copy.  The buffers are job_verify_impl's (a context runs one call at a time).
+// The caller's arrays are written last.
+int pool_verify_impl(bm_ctx* ctx, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                     const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                     bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out) {
+    if (!g_pool_verify) return BM_EINTERNAL;
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    PoolVerifyArgs A;
+    std::vector<uint32_t> tail, branch;
+    host::pool_verify_prepare(job, A, tail, branch);
+    A.n = (uint32_t)n;
+    A.nsessions = (uint32_t)nsessions;
+    A.ntime_lo = ntime_lo;
+    A.ntime_hi = ntime_hi;
+    // device buffer, in 8-byte units: tail | branch | sessions | submits | verdicts.  An empty table is
+    // staged as one zero session: a lane whose index is out of range reads entry 0 and stores INVALID
+    const size_t staged = nsessions ? nsessions : 1;
+    const size_t tail_u = tail.size() / 2, branch_u = branch.size() / 2;
+    const size_t ses_u = staged * sizeof(bm_pool_session_t) / 8, sub_u = n * sizeof(bm_pool_submit_t) / 8;
+    const size_t in_u = tail_u + branch_u + ses_u + sub_u;
+    const size_t out_u = n * sizeof(bm_job_verdict_t) / 8;
+    BM_TRY(grow(d, d.h_verify, d.hverify_cap, in_u + out_u, sizeof(uint64_t), true));
+    BM_TRY(grow(d, d.d_verify, d.verify_cap, in_u + out_u));
+    uint64_t* stage = d.h_verify;
+    const bm_job_verdict_t* got = reinterpret_cast<const bm_job_verdict_t*>(d.h_verify + in_u);
+    std::memcpy(stage, tail.data(), 8 * tail_u);
+    if (branch_u) std::memcpy(stage + tail_u, branch.data(), 8 * branch_u);
+    if (nsessions)
+        std::memcpy(stage + tail_u + branch_u, sessions, 8 * ses_u);
+    else
+        std::memset(stage + tail_u + branch_u, 0, 8 * ses_u);
+    std::memcpy(stage + tail_u + branch_u + ses_u, submits, 8 * sub_u);
+    BM_HIP(hipMemcpyAsync(d.d_verify, stage, 8 * in_u, hipMemcpyHostToDevice, d.stream));
+    const uint32_t* d_tail = reinterpret_cast<const uint32_t*>(d.d_verify);
+    const uint32_t* d_branch = reinterpret_cast<const uint32_t*>(d.d_verify + tail_u);
+    const uint32_t* d_ses = reinterpret_cast<const uint32_t*>(d.d_verify + tail_u + branch_u);
+    const bm_pool_submit_t* d_sub = reinterpret_cast<const bm_pool_submit_t*>(d.d_verify + tail_u + branch_u + ses_u);
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(d.d_verify + in_u);
+    const uint32_t grid = (uint32_t)((n + 63) / 64);
+    void* args[] = {&A, &d_tail, &d_branch, &d_ses, &d_sub, &d_out};
+    BM_HIP(hipLaunchKernel(g_pool_verify, dim3(grid), dim3(64), args, 0, d.stream));
+    BM_HIP(hipMemcpyAsync(d.h_verify + in_u, d_out, 8 * out_u, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    // the tripwire: the ends of the batch and every claimed block, by the CPU path
+    uint8_t bt[32];
+    const uint8_t* block_target = host::target_from_bits(job->nbits, bt) ? bt : nullptr;
+    for (size_t i = 0; i < n; ++i) {
+        if (i != 0 && i != n - 1 && !(got[i].status & BM_SUBMIT_BLOCK)) continue;
+        bm_job_verdict_t want;
+        host::pool_verify_one(job, sessions, nsessions, block_target, ntime_lo, ntime_hi, submits[i], want);
+        if (std::memcmp(&want, &got[i], sizeof want) != 0) return BM_EINTERNAL;
+    }
+    bm_pool_verify_result_t r;
+    host::pool_verify_count(got, n, r);
+    std::memcpy(verdicts, got, n * sizeof(bm_job_verdict_t));
+    *out = r;
+    return BM_OK;
+}
+
 }  // namespace
 }  // namespace bm
 
 extern "C" {
+
+void bm_register_pool_verify_kernel(const void* fn) { bm::g_pool_verify = fn; }
+
+int bm_pool_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                       const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                       bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out) {
+    if (!ctx) return BM_EINVAL;
+    const int rc = bm::host::pool_verify_check(job, sessions, nsessions, submits, n, verdicts, out);
+    if (rc != BM_OK) return rc;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    if (n == 0) {
+        std::memset(out, 0, sizeof *out);
+        return BM_OK;
+    }
+    bm::DeviceGuard guard;
+    return bm::guarded([&] {
+        return bm::pool_verify_impl(ctx, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, verdicts, out);
+    });
+}
 
 void bm_register_job_verify_kernel(const void* fn) { bm::g_job_verify = fn; }
 

@@ -1,8 +1,8 @@
 // bm_job.cpp -- the pure-CPU entries of the Stratum job layer (include/btcminer.h):
 // bm_job_prevhash_from_stratum, bm_job_header, bm_job_verify_cpu,
-// bm_target_from_difficulty.  They need no context and no GPU;
+// bm_pool_verify_cpu, bm_target_from_difficulty.  They need no context and no GPU;
 // bm_search_job_shares_gpu (bm_search.cpp) builds its headers and
-// bm_job_verify_gpu (bm_aux.hip) checks its device with the same code
+// bm_job_verify_gpu and bm_pool_verify_gpu (bm_aux.hip) check their device with the same code
 // (bm_job.hpp).  Plain C++: no HIP in here.
 #include "bm_job.hpp"
 
@@ -40,6 +40,21 @@ int bm_job_verify_cpu(const bm_job_t* job, const uint8_t target[32], const bm_jo
     const uint8_t* block_target = bm::host::target_from_bits(job->nbits, bt) ? bt : nullptr;
     for (size_t i = 0; i < n; ++i) bm::host::verify_one(job, target, block_target, submits[i], verdicts[i]);
     bm::host::verify_count(verdicts, n, *out);
+    return BM_OK;
+}
+
+// The specification of bm_pool_verify_gpu: bm_job_verify_cpu with extranonce1 and
+// the share target taken from the submission's session, and the ntime window.
+int bm_pool_verify_cpu(const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                       const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                       bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out) {
+    const int rc = bm::host::pool_verify_check(job, sessions, nsessions, submits, n, verdicts, out);
+    if (rc != BM_OK) return rc;
+    uint8_t bt[32];
+    const uint8_t* block_target = bm::host::target_from_bits(job->nbits, bt) ? bt : nullptr;
+    for (size_t i = 0; i < n; ++i)
+        bm::host::pool_verify_one(job, sessions, nsessions, block_target, ntime_lo, ntime_hi, submits[i], verdicts[i]);
+    bm::host::pool_verify_count(verdicts, n, *out);
     return BM_OK;
 }
 

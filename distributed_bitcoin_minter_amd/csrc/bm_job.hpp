@@ -4,10 +4,13 @@
 // version-rolling share enumeration become one list and one best share
 // (JobMerge).  And the host's half of share verification (bm_job_verify_cpu,
 // bm_job_verify_gpu): one submission's verdict on the CPU, and what
-// job_verify_kernel (bm_job_verify.hpp) takes of a job.  Shared by the launcher
-// (bm_search.cpp), bm_aux.hip, the pure-CPU entries (bm_job.cpp) and two
-// stand-alone CPU checks (tools/job_check.cpp, tools/verify_check.cpp).  Plain
-// C++: no HIP in here (en2_words alone is marked for both sides).
+// job_verify_kernel (bm_job_verify.hpp) takes of a job; the same for one job's
+// submissions from many sessions (bm_pool_verify_cpu, bm_pool_verify_gpu,
+// pool_verify_kernel in bm_pool_verify.hpp).  Shared by the launcher
+// (bm_search.cpp), bm_aux.hip, the pure-CPU entries (bm_job.cpp) and three
+// stand-alone CPU checks (tools/job_check.cpp, tools/verify_check.cpp,
+// tools/pool_verify_check.cpp).  Plain C++: no HIP in here (en2_words and
+// field_words alone are marked for both sides).
 //
 //   coinbase = coinb1 || extranonce1 || BE(extranonce2, extranonce2_size) || coinb2
 //   root     = sha256d(coinbase); for each branch entry: root = sha256d(root || entry)
@@ -332,6 +335,156 @@ private:
     std::vector<bm_job_share_t> list_;
     bm_job_shares_result_t out_;
 };
+
+}  // namespace host
+
+// ---- share verification across sessions (bm_pool_verify_cpu / bm_pool_verify_gpu) ----
+// One job, many sessions: extranonce1 and the share target are per-submission
+// data, looked up in a session table.  The varying field of the coinbase is now
+//   extranonce1 || BE(extranonce2, extranonce2_size),
+// 2..16 bytes that start at byte coinb1_len.  The host hashes the whole blocks
+// that end before coinb1_len once (mid) and lays the rest out as a padded tail
+// with BOTH fields zero; a lane ORs its field into the up to five consecutive
+// words it can touch (16 bytes at byte 3 of a word are 19 bytes), which may
+// cross a block edge.
+
+// Kernel argument of pool_verify_kernel, by value (SGPRs).
+struct PoolVerifyArgs {
+    uint32_t mid[8];    // state after the whole blocks before the field's block
+    uint32_t prev[8];   // prevhash as big-endian words (header words 1..8)
+    uint32_t btgt[8];   // the target of nbits, most significant word first (has_block)
+    uint32_t nbits;
+    uint32_t has_block; // 1: nbits decodes
+    uint32_t nb;        // 64-byte blocks of the tail (1..1025)
+    uint32_t j0;        // first tail word the field touches (0..15)
+    uint32_t boff;      // the field's byte offset in that word (0..3)
+    uint32_t size1;     // extranonce1_len (1..8)
+    uint32_t size2;     // extranonce2_size (1..8)
+    uint32_t depth;     // branch entries (0..32)
+    uint32_t n;         // submissions
+    uint32_t nsessions; // entries of the session table a lane may pick (the table on the device has at least one)
+    uint32_t ntime_lo, ntime_hi;
+};
+
+static_assert(sizeof(bm_pool_session_t) == 40, "session layout");
+static_assert(sizeof(bm_pool_submit_t) == 24, "pool submit layout");
+constexpr int kSessionWords = 10;  // a session as the kernel loads it: 2 words of extranonce1, 8 of the target
+constexpr int kFieldWords = 5;
+
+// The field extranonce1 (its first size1 bytes: en1 holds the session's eight
+// bytes as a big-endian integer, byte 0 on top) || extranonce2 (size2 bytes,
+// big-endian) at byte boff of a 20-byte window, as the window's five big-endian
+// words.
+BM_HD inline void field_words(uint64_t en1, uint32_t size1, uint64_t extranonce2, uint32_t size2, uint32_t boff,
+                              uint32_t (&e)[kFieldWords]) {
+    const uint64_t v1 = en1 & (~0ull << (8 * (8 - size1)));   // the bytes that count, the first on top
+    const uint64_t v2 = extranonce2 << (8 * (8 - size2));      // likewise
+    // the field as 16 bytes, its first byte on top of hi
+    const uint64_t hi = v1 | (size1 < 8 ? v2 >> (8 * size1) : 0ull);
+    const uint64_t lo = v2 << (8 * (8 - size1));
+    // each window word is 32 bits of the 64-bit pair around it, boff bytes down
+    const uint64_t mid = (hi << 32) | (lo >> 32);
+    const uint32_t s = 8 * boff;
+    e[0] = (uint32_t)((hi >> 32) >> s);
+    e[1] = (uint32_t)(hi >> s);
+    e[2] = (uint32_t)(mid >> s);
+    e[3] = (uint32_t)(lo >> s);
+    e[4] = (uint32_t)((lo << 32) >> s);
+}
+
+namespace host {
+
+// A session's extranonce1 bytes as field_words takes them.
+inline uint64_t session_en1(const bm_pool_session_t& s) {
+    return ((uint64_t)load_be32(s.extranonce1) << 32) | load_be32(s.extranonce1 + 4);
+}
+
+// What both pool entries refuse, ctx aside.  job->extranonce1 is not looked at.
+inline int pool_verify_check(const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                             const bm_pool_submit_t* submits, size_t n, const bm_job_verdict_t* verdicts,
+                             const bm_pool_verify_result_t* out) {
+    if (!job || !out || n > BM_MAX_JOB_SUBMITS || nsessions > BM_MAX_POOL_SESSIONS) return BM_EINVAL;
+    if ((n && (!submits || !verdicts)) || (nsessions && !sessions)) return BM_EINVAL;
+    if (job->extranonce1_len < 1 || job->extranonce1_len > 8) return BM_EINVAL;
+    bm_job_t j = *job;
+    j.extranonce1 = j.prevhash;  // any non-NULL pointer: job_check reads no byte of it
+    return job_check(&j);
+}
+
+// What pool_verify_kernel takes of a checked job (pool_verify_check): A but for
+// n, nsessions and the window, the tail's words (16 * A.nb) and the branch's
+// (8 * A.depth), both big-endian.
+inline void pool_verify_prepare(const bm_job_t* job, PoolVerifyArgs& A, std::vector<uint32_t>& tail,
+                                std::vector<uint32_t>& branch) {
+    std::memset(&A, 0, sizeof A);
+    const size_t pos = job->coinb1_len;  // the field's first byte
+    const size_t size = job->extranonce1_len + job->extranonce2_size;
+    const size_t total = pos + size + job->coinb2_len;
+    const size_t pre = pos / 64;         // whole blocks before its block
+    const size_t padded = (total + 9 + 63) / 64 * 64;
+    std::vector<uint8_t> bytes(padded, 0);
+    if (job->coinb1_len) std::memcpy(bytes.data(), job->coinb1, job->coinb1_len);
+    if (job->coinb2_len) std::memcpy(bytes.data() + pos + size, job->coinb2, job->coinb2_len);
+    bytes[total] = 0x80;
+    const uint64_t bits = (uint64_t)total * 8;
+    for (int i = 0; i < 8; ++i) bytes[padded - 8 + i] = (uint8_t)(bits >> (8 * (7 - i)));
+    uint32_t st[8];
+    for (int i = 0; i < 8; ++i) st[i] = kIV256[i];
+    for (size_t b = 0; b < pre; ++b) compress_bytes(st, bytes.data() + 64 * b);
+    for (int i = 0; i < 8; ++i) A.mid[i] = st[i];
+    A.nb = (uint32_t)(padded / 64 - pre);
+    const size_t off = pos - 64 * pre;
+    A.j0 = (uint32_t)(off / 4);
+    A.boff = (uint32_t)(off % 4);
+    A.size1 = (uint32_t)job->extranonce1_len;
+    A.size2 = job->extranonce2_size;
+    A.depth = (uint32_t)job->nbranch;
+    tail.resize(16 * (size_t)A.nb);
+    for (size_t k = 0; k < tail.size(); ++k) tail[k] = load_be32(bytes.data() + 64 * pre + 4 * k);
+    branch.resize(8 * job->nbranch);
+    for (size_t k = 0; k < branch.size(); ++k) branch[k] = load_be32(job->branch + 4 * k);
+    for (int k = 0; k < 8; ++k) A.prev[k] = load_be32(job->prevhash + 4 * k);
+    A.nbits = job->nbits;
+    uint8_t bt[32];
+    A.has_block = target_from_bits(job->nbits, bt) ? 1u : 0u;
+    if (A.has_block)
+        for (int k = 0; k < 8; ++k) A.btgt[k] = load_be32(bt + 4 * k);
+}
+
+// The verdict of one submission of a checked job: the CPU path.  block_target as
+// in verify_one.
+inline void pool_verify_one(const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                            const uint8_t* block_target, uint32_t ntime_lo, uint32_t ntime_hi,
+                            const bm_pool_submit_t& s, bm_job_verdict_t& v) {
+    std::memset(&v, 0, sizeof v);
+    if (s.session >= nsessions || !extranonce2_fits(s.extranonce2, job->extranonce2_size)) {
+        std::memset(v.hash, 0xFF, sizeof v.hash);
+        v.status = BM_SUBMIT_INVALID;
+        return;
+    }
+    const bm_pool_session_t& ses = sessions[s.session];
+    bm_job_t j = *job;
+    j.extranonce1 = ses.extranonce1;
+    uint8_t header[kHeaderBytes];
+    job_header(&j, s.extranonce2, s.ntime, s.version, header);
+    header_hash_msb(header, s.nonce, v.hash);
+    if (std::memcmp(v.hash, ses.target, 32) <= 0) v.status |= BM_SUBMIT_SHARE;
+    if (block_target && std::memcmp(v.hash, block_target, 32) <= 0) v.status |= BM_SUBMIT_BLOCK;
+    if (s.ntime < ntime_lo || s.ntime > ntime_hi) v.status |= BM_SUBMIT_NTIME;
+}
+
+// *out of a pool call from its verdicts.
+inline void pool_verify_count(const bm_job_verdict_t* verdicts, size_t n, bm_pool_verify_result_t& out) {
+    std::memset(&out, 0, sizeof out);
+    out.n = n;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t st = verdicts[i].status;
+        out.shares += (st & BM_SUBMIT_SHARE) ? 1 : 0;
+        out.blocks += (st & BM_SUBMIT_BLOCK) ? 1 : 0;
+        out.invalid += (st & BM_SUBMIT_INVALID) ? 1 : 0;
+        out.ntime += (st & BM_SUBMIT_NTIME) ? 1 : 0;
+    }
+}
 
 }  // namespace host
 }  // namespace bm

@@ -26,34 +26,12 @@
 // A lane whose extranonce2 does not fit its field runs along (its words are
 // masked to nothing) and stores the INVALID verdict instead.
 #pragma once
-#include "bm_header_kernels.hpp"
 #include "bm_job.hpp"
+#include "bm_verify_kernels.hpp"  // digest_block, set_iv, hash_digest: pool_verify_kernel's too
 
 namespace bm {
 
 constexpr int kJobVerifyThreads = 64;
-
-// w[0..7] = d, then the padding of a 32-byte message: the second hash's block.
-BM_DEV void digest_block(const uint32_t (&d)[8], uint32_t (&w)[16]) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = d[k];
-    w[8] = 0x80000000u;
-#pragma unroll
-    for (int k = 9; k < 15; ++k) w[k] = 0;
-    w[15] = 256u;
-}
-
-BM_DEV void set_iv(uint32_t (&st)[8]) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) st[k] = kIV256[k];
-}
-
-// st = SHA256 state of the 32 bytes st held as a digest: the second hash.
-BM_DEV void hash_digest(uint32_t (&st)[8], uint32_t (&w)[16]) {
-    digest_block(st, w);
-    set_iv(st);
-    sha_compress(st, w);
-}
 
 __global__ __launch_bounds__(kJobVerifyThreads) void job_verify_kernel(const JobVerifyArgs A,
                                                                         const uint32_t* __restrict__ tail,

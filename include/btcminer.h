@@ -598,8 +598,10 @@ int bm_search_job_shares_gpu(bm_ctx_t* ctx, const bm_job_t* job, uint32_t ntime,
  * the result -- everything else is the device's claim.  bm_ctx_last_stats is left
  * as the previous call left it.
  *
- * Out of scope: duplicate detection across batches; an ntime window; vardiff; a
- * network Stratum server; splitting a batch over devices; rank groups. */
+ * Out of scope: duplicate detection across batches; vardiff; a network Stratum
+ * server; splitting a batch over devices; rank groups.  Submissions of many
+ * sessions (an extranonce1 and a target each) in one call, and an ntime window:
+ * bm_pool_verify_gpu, below. */
 #define BM_MAX_JOB_SUBMITS (1u << 20)
 #define BM_SUBMIT_SHARE 1u   /* hash <= target */
 #define BM_SUBMIT_BLOCK 2u   /* hash <= the target of job->nbits (needs a decodable nbits) */
@@ -624,6 +626,82 @@ int bm_job_verify_cpu(const bm_job_t* job, const uint8_t target[32], const bm_jo
                       bm_job_verdict_t* verdicts, bm_job_verify_result_t* out);
 int bm_job_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const uint8_t target[32], const bm_job_submit_t* submits,
                       size_t n, bm_job_verdict_t* verdicts, bm_job_verify_result_t* out);
+
+/* ---- pool-side share verification across sessions: one job, many workers --------
+ * A pool sends the same job to every connection; each connection has its own
+ * extranonce1 and its own difficulty.  bm_pool_verify_gpu is bm_job_verify_gpu with
+ * extranonce1 and the share target as per-submission data: submits[i].session picks
+ * sessions[s], and an ntime window is checked along the way.  One call covers one
+ * job's submissions from every session; bm_job_verify_* is unchanged beside it.
+ *
+ *   job->extranonce1 is ignored and may be NULL.  job->extranonce1_len is the size
+ *     of EVERY session's extranonce1 and must be 1..8: the first extranonce1_len
+ *     bytes of sessions[s].extranonce1 count, the rest are ignored.  Everything
+ *     else about the job is checked as bm_job_header checks it.
+ *   verdicts[i] belongs to submits[i]; the order is the caller's.  verdicts reuses
+ *     bm_job_verdict_t.
+ *   verdicts[i].hash = H of bm_job_header for that same job with extranonce1 =
+ *     sessions[s].extranonce1, under the submission's (extranonce2, ntime, version:
+ *     the full header field), with nonce in bytes 76..79, most significant byte
+ *     first.
+ *   verdicts[i].status = the OR of
+ *     BM_SUBMIT_SHARE   hash <= sessions[s].target,
+ *     BM_SUBMIT_BLOCK   hash <= bm_header_target_from_bits(job->nbits), as in
+ *                       bm_job_verify_gpu (independent of SHARE; clear everywhere
+ *                       for an nbits that does not decode),
+ *     BM_SUBMIT_NTIME   ntime < ntime_lo || ntime > ntime_hi.  It is OR-ed in: the
+ *                       hash and the other flags are computed all the same, and the
+ *                       caller decides what to do with a share outside the window.
+ *                       A caller who wants no window passes 0, 0xFFFFFFFF;
+ *                       ntime_lo > ntime_hi flags every hashed entry,
+ *     BM_SUBMIT_INVALID extranonce2 >= 2^(8 * extranonce2_size), or session >=
+ *                       nsessions: nothing is hashed, hash is all 0xFF and status
+ *                       is exactly this flag (no NTIME either),
+ *     both compares over the full 256 bits.  verdicts[i].reserved = 0.
+ *   out: n and how many verdicts carry each flag.
+ *   n == 0 succeeds with a zero *out and touches no array (submits and verdicts may
+ *     be NULL).  nsessions == 0 with n > 0 is legal (sessions may be NULL then):
+ *     every entry is INVALID.
+ *   Duplicate detection stays the caller's: a pool needs it across batches anyway.
+ * BM_EINVAL: n > BM_MAX_JOB_SUBMITS or nsessions > BM_MAX_POOL_SESSIONS; a NULL
+ * job or out (or ctx); NULL submits or verdicts with n > 0; NULL sessions with
+ * nsessions > 0; extranonce1_len outside 1..8; a job bm_job_header refuses
+ * otherwise; a rank context with world > 1.  On any failure `verdicts` and `out`
+ * are untouched and the context stays usable.
+ *
+ * bm_pool_verify_cpu is pure CPU, no context: the specification.
+ * bm_pool_verify_gpu gives byte-identical `verdicts` and `out`, on the first device
+ * of ctx: one host-to-device copy (the job's tail template, its branch, the session
+ * table and the submissions), one launch of pool_verify_kernel (one lane per
+ * submission) and one copy back, on that device's stream.  The host then
+ * recomputes entry 0, entry n - 1 and every entry flagged BLOCK with the CPU path
+ * and returns BM_EINTERNAL on any difference: a tripwire, not the result.
+ * bm_ctx_last_stats is left as the previous call left it.
+ *
+ * Out of scope: duplicate detection; vardiff policy; a network Stratum server;
+ * several jobs in one call; splitting a batch over devices; rank groups. */
+#define BM_MAX_POOL_SESSIONS (1u << 20)
+#define BM_SUBMIT_NTIME 8u            /* ntime outside [ntime_lo, ntime_hi]; hashed all the same */
+typedef struct bm_pool_session {
+    uint8_t extranonce1[8];           /* the first job->extranonce1_len bytes count */
+    uint8_t target[32];               /* this session's share target, most significant byte first */
+} bm_pool_session_t;                  /* 40 bytes */
+typedef struct bm_pool_submit {
+    uint64_t extranonce2;
+    uint32_t ntime, nonce, version;   /* version: the full header field, as in bm_job_submit_t */
+    uint32_t session;                 /* index into sessions[] */
+} bm_pool_submit_t;                   /* 24 bytes, bm_job_submit_t's layout with reserved put to use */
+typedef struct bm_pool_verify_result {
+    uint64_t n;                       /* submissions */
+    uint64_t shares, blocks, invalid, ntime; /* verdicts with BM_SUBMIT_SHARE / _BLOCK / _INVALID / _NTIME */
+} bm_pool_verify_result_t;            /* 40 bytes */
+
+int bm_pool_verify_cpu(const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                       const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                       bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out);
+int bm_pool_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                       const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                       bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out);
 
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */

@@ -112,6 +112,24 @@ inline bm_job_verify_result_t verify_job_submits_cpu(const Job& job, const uint8
     return r;
 }
 
+// Context::verify_pool_submits without a GPU or a context: bm_pool_verify_cpu, the
+// specification of the GPU entry.  job.extranonce1 gives the size of every
+// session's extranonce1 (1..8 bytes); its bytes are not used
+inline bm_pool_verify_result_t verify_pool_submits_cpu(const Job& job, const std::vector<bm_pool_session_t>& sessions,
+                                                       const bm_pool_submit_t* submits, size_t n,
+                                                       std::vector<bm_job_verdict_t>& verdicts, uint32_t ntime_lo = 0,
+                                                       uint32_t ntime_hi = 0xFFFFFFFFu) {
+    if (job.branch.size() % 32 != 0) throw Error(BM_EINVAL, "verify_pool_submits_cpu");
+    const bm_job_t j = job.view();
+    bm_pool_verify_result_t r;
+    std::vector<bm_job_verdict_t> buf(n);
+    check(bm_pool_verify_cpu(&j, sessions.empty() ? nullptr : sessions.data(), sessions.size(), submits, n, ntime_lo,
+                             ntime_hi, n ? buf.data() : nullptr, &r),
+          "bm_pool_verify_cpu");
+    verdicts = std::move(buf);
+    return r;
+}
+
 // Owns a bm_ctx.  Not thread-safe, like the C context (one per OS thread).
 class Context {
    public:
@@ -282,6 +300,24 @@ class Context {
         bm_job_verify_result_t r;
         std::vector<bm_job_verdict_t> buf(n);
         check(bm_job_verify_gpu(ctx_, &j, target, submits, n, n ? buf.data() : nullptr, &r), "bm_job_verify_gpu");
+        verdicts = std::move(buf);
+        return r;
+    }
+    // one job's submissions from many sessions (an extranonce1 and a share target
+    // each, picked by submits[i].session), with an ntime window: one verdict per
+    // submission into `verdicts` (resized to n) and the count of each flag, on the
+    // first device: bm_pool_verify_gpu
+    bm_pool_verify_result_t verify_pool_submits(const Job& job, const std::vector<bm_pool_session_t>& sessions,
+                                                const bm_pool_submit_t* submits, size_t n,
+                                                std::vector<bm_job_verdict_t>& verdicts, uint32_t ntime_lo = 0,
+                                                uint32_t ntime_hi = 0xFFFFFFFFu) {
+        if (job.branch.size() % 32 != 0) throw Error(BM_EINVAL, "verify_pool_submits");
+        const bm_job_t j = job.view();
+        bm_pool_verify_result_t r;
+        std::vector<bm_job_verdict_t> buf(n);
+        check(bm_pool_verify_gpu(ctx_, &j, sessions.empty() ? nullptr : sessions.data(), sessions.size(), submits, n,
+                                 ntime_lo, ntime_hi, n ? buf.data() : nullptr, &r),
+              "bm_pool_verify_gpu");
         verdicts = std::move(buf);
         return r;
     }
