@@ -10,11 +10,12 @@ re-built as gfx950 HIP kernels behind the C ABI in include/btcminer.h
         print(m.search("bradfitz", 0, 9999))   # (1419516646206828, 9898)
 """
 from . import bitcoin, dist
-from ._lib import (BtcMinerError, Context, HeaderHit, HeaderHitsResult, HeaderVersionHit, HeaderVersionsHitsResult,
-                   HeaderVersionsResult, HitsResult, Job, JobShare, JobSharesResult, JobSubmit, JobVerdict,
-                   JobVerifyResult, LIB_PATH, PoolSession, PoolSubmit, PoolVerifyResult, bits_to_target, device_count,
-                   difficulty_to_target, parse_pool_submit, parse_submit, plan_segments, rccl_unique_id, roll_versions,
-                   submit_params, verify_pool_submits_cpu, verify_submits_cpu)
+from ._lib import (BM_EFULL, BM_MAX_SHARE_SET, BM_SUBMIT_DUPLICATE, BtcMinerError, Context, HeaderHit, HeaderHitsResult,
+                   HeaderVersionHit, HeaderVersionsHitsResult, HeaderVersionsResult, HitsResult, Job, JobShare,
+                   JobSharesResult, JobSubmit, JobVerdict, JobVerifyResult, LIB_PATH, PoolSession, PoolSubmit,
+                   PoolVerifyResult, ShareSet, ShareSetResult, bits_to_target, device_count, difficulty_to_target,
+                   parse_pool_submit, parse_submit, plan_segments, rccl_unique_id, roll_versions, submit_params,
+                   verify_pool_submits_cpu, verify_submits_cpu)
 from .miner import Miner
 
 __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", "HeaderHitsResult",
@@ -22,4 +23,5 @@ __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", 
            "JobSharesResult", "JobSubmit", "JobVerdict", "JobVerifyResult", "LIB_PATH", "bits_to_target", "device_count",
            "difficulty_to_target", "parse_submit", "plan_segments", "rccl_unique_id", "roll_versions", "submit_params",
            "verify_submits_cpu", "PoolSession", "PoolSubmit", "PoolVerifyResult", "parse_pool_submit",
-           "verify_pool_submits_cpu"]
+           "verify_pool_submits_cpu", "ShareSet", "ShareSetResult", "BM_SUBMIT_DUPLICATE", "BM_EFULL",
+           "BM_MAX_SHARE_SET"]

@@ -21,6 +21,7 @@ BM_ENOMEM = -5
 BM_EINTERNAL = -6
 BM_EPEER = -7
 BM_ETIMEDOUT = -8
+BM_EFULL = -9
 BM_MAX_LAUNCH_STATS = 64
 BM_MAX_STAT_DEVICES = 16
 BM_RCCL_ID_BYTES = 128
@@ -178,6 +179,11 @@ class JobVerdict(ctypes.Structure):
         """ntime outside the window (Context.verify_pool_submits only)."""
         return bool(self.status & 8)  # BM_SUBMIT_NTIME
 
+    @property
+    def is_duplicate(self) -> bool:
+        """An eligible hash the share set already held (ShareSet.verify only)."""
+        return bool(self.status & 16)  # BM_SUBMIT_DUPLICATE
+
 
 class JobVerifyResult(ctypes.Structure):
     _fields_ = [("n", c_u64), ("shares", c_u64), ("blocks", c_u64), ("invalid", c_u64)]
@@ -223,6 +229,17 @@ class PoolSubmit(ctypes.Structure):
 
 class PoolVerifyResult(ctypes.Structure):
     _fields_ = [("n", c_u64), ("shares", c_u64), ("blocks", c_u64), ("invalid", c_u64), ("ntime", c_u64)]
+
+
+BM_SUBMIT_DUPLICATE = 16
+BM_MAX_SHARE_SET = 1 << 24
+
+
+class ShareSetResult(ctypes.Structure):
+    """bm_share_set_result_t: PoolVerifyResult's counts, then the verdicts flagged
+    DUPLICATE, the hashes the call added and the set's size after it."""
+    _fields_ = [("n", c_u64), ("shares", c_u64), ("blocks", c_u64), ("invalid", c_u64), ("ntime", c_u64),
+                ("duplicates", c_u64), ("recorded", c_u64), ("count", c_u64)]
 
 
 class Segment(ctypes.Structure):
@@ -323,6 +340,13 @@ def _open(path):
                                 c_u32, c_u32, P(JobVerdict), P(PoolVerifyResult)], ctypes.c_int),
         "bm_pool_verify_gpu": ([vp, P(JobStruct), P(PoolSessionStruct), ctypes.c_size_t, P(PoolSubmit),
                                 ctypes.c_size_t, c_u32, c_u32, P(JobVerdict), P(PoolVerifyResult)], ctypes.c_int),
+        "bm_share_set_create": ([vp, ctypes.c_size_t, P(vp)], ctypes.c_int),
+        "bm_share_set_create_cpu": ([ctypes.c_size_t, P(vp)], ctypes.c_int),
+        "bm_share_set_destroy": ([vp], None),
+        "bm_share_set_clear": ([vp], ctypes.c_int),
+        "bm_share_set_count": ([vp, P(c_u64), P(c_u64)], ctypes.c_int),
+        "bm_share_set_verify": ([vp, P(JobStruct), P(PoolSessionStruct), ctypes.c_size_t, P(PoolSubmit), ctypes.c_size_t,
+                                 c_u32, c_u32, P(JobVerdict), P(ShareSetResult)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -679,7 +703,7 @@ def _pool_submit_array(submits):
     return arr
 
 
-def _pool_verify(call, what, job, sessions, submits, ntime_lo, ntime_hi):
+def _pool_verify(call, what, job, sessions, submits, ntime_lo, ntime_hi, result=None):
     if not isinstance(job, Job):
         raise ValueError("job must be a Job")
     if not 1 <= len(job.extranonce1) <= 8:
@@ -692,7 +716,7 @@ def _pool_verify(call, what, job, sessions, submits, ntime_lo, ntime_hi):
         raise ValueError(f"at most {BM_MAX_POOL_SESSIONS} sessions per call, got {len(ses)}")
     _u32(ntime_lo, "ntime_lo"), _u32(ntime_hi, "ntime_hi")
     verdicts = (JobVerdict * len(arr))()
-    r = PoolVerifyResult()
+    r = (result or PoolVerifyResult)()
     check(call(ctypes.byref(job.struct), ses if len(ses) else None, len(ses), arr if len(arr) else None, len(arr),
                ntime_lo, ntime_hi, verdicts if len(arr) else None, ctypes.byref(r)), what)
     return verdicts, r
@@ -702,6 +726,85 @@ def verify_pool_submits_cpu(job, sessions, submits, ntime_lo: int = 0, ntime_hi:
     """Context.verify_pool_submits without a GPU or a context (bm_pool_verify_cpu,
     pure CPU): the specification of the GPU entry, byte-identical to it."""
     return _pool_verify(load().bm_pool_verify_cpu, "bm_pool_verify_cpu", job, sessions, submits, ntime_lo, ntime_hi)
+
+
+class ShareSet:
+    """A bm_share_set_t: the set of header hashes behind duplicate-share detection,
+    by convention one job's.  ShareSet(ctx, capacity) lives on the first device of
+    ctx, across calls, and is closed before ctx; ShareSet.cpu(capacity) lives in
+    host memory and needs no GPU: the specification.  Not thread-safe, and a device
+    set shares its context's buffers: one call at a time per context."""
+
+    def __init__(self, ctx, capacity: int, lib_path=None):
+        self._h = None
+        if not isinstance(capacity, int) or isinstance(capacity, bool) or not 1 <= capacity <= BM_MAX_SHARE_SET:
+            raise ValueError(f"capacity must be in 1..{BM_MAX_SHARE_SET}, got {capacity!r}")
+        h = ctypes.c_void_p()
+        if ctx is None:
+            self._lib = load(lib_path)
+            check(self._lib.bm_share_set_create_cpu(capacity, ctypes.byref(h)), "bm_share_set_create_cpu")
+        else:
+            self._lib = ctx._lib
+            check(self._lib.bm_share_set_create(ctx.handle, capacity, ctypes.byref(h)), "bm_share_set_create")
+        self._ctx = ctx  # a device set must not outlive its context
+        self._h = h
+
+    @classmethod
+    def cpu(cls, capacity: int, lib_path=None):
+        """A set in host memory (bm_share_set_create_cpu)."""
+        return cls(None, capacity, lib_path)
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("share set closed")
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            if self._ctx is None or self._ctx._h is not None:  # (a closed context took the device's memory with it)
+                self._lib.bm_share_set_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _sizes(self):
+        count, capacity = c_u64(0), c_u64(0)
+        check(self._lib.bm_share_set_count(self.handle, ctypes.byref(count), ctypes.byref(capacity)), "bm_share_set_count")
+        return count.value, capacity.value
+
+    @property
+    def count(self) -> int:
+        """Hashes the set holds."""
+        return self._sizes()[0]
+
+    @property
+    def capacity(self) -> int:
+        return self._sizes()[1]
+
+    def clear(self):
+        """Forget every hash: a new job."""
+        check(self._lib.bm_share_set_clear(self.handle), "bm_share_set_clear")
+
+    def verify(self, job, sessions, submits, ntime_lo: int = 0, ntime_hi: int = (1 << 32) - 1):
+        """Context.verify_pool_submits plus the set (bm_share_set_verify) ->
+        (verdicts, ShareSetResult): an eligible submission (SHARE or BLOCK, not
+        INVALID) whose hash the set holds, from an earlier call or a lower index of
+        this one, carries BM_SUBMIT_DUPLICATE; the others are recorded.  All or
+        nothing: BtcMinerError with status BM_EFULL when the batch's new hashes do
+        not fit, and the set is as before."""
+        return _pool_verify(lambda *a: self._lib.bm_share_set_verify(self.handle, *a), "bm_share_set_verify", job,
+                            sessions, submits, ntime_lo, ntime_hi, ShareSetResult)
 
 
 def _header_bytes(header) -> bytes:

@@ -1,9 +1,10 @@
 // bm_aux.hip -- the one unit of the host runtime with device code: the small
 // kernels of bm_aux_kernels.hpp, the host wrapper the searches launch the
 // second-pass reduction through, and the entry points outside the search
-// path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu, and bm_job_verify_gpu
-// and bm_pool_verify_gpu, whose kernels have units of their own,
-// bm_job_verify_inst.hip and bm_pool_verify_inst.hip).  See
+// path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu, and bm_job_verify_gpu,
+// bm_pool_verify_gpu and the device side of bm_share_set_verify, whose kernels have
+// units of their own, bm_job_verify_inst.hip, bm_pool_verify_inst.hip and
+// bm_share_set_inst.hip).  See
 // bm_runtime.hpp for the layout of the host runtime.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,7 @@
 #include "bm_aux_kernels.hpp"
 #include "bm_job.hpp"
 #include "bm_runtime.hpp"
+#include "bm_share_set_host.hpp"
 
 namespace bm {
 
@@ -184,17 +186,26 @@ int job_verify_impl(bm_ctx* ctx, const bm_job_t* job, const uint8_t* target, con
 // pool_verify_kernel, registered by bm_pool_verify_inst.hip at load time
 const void* g_pool_verify = nullptr;
 
-// bm_pool_verify_gpu on the first device, the shape of job_verify_impl: the job's
-// tail template, its branch, the session table and the submissions go up in one
-// copy, one launch gives a lane to each submission, the verdicts come back in one
-// copy.  The buffers are job_verify_impl's (a context runs one call at a time).
-// The caller's arrays are written last.
-int pool_verify_impl(bm_ctx* ctx, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
-                     const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
-                     bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out) {
+// What bm_pool_verify_gpu and bm_share_set_verify share: the stage, the launch of
+// pool_verify_kernel, and the tripwire.  The job's tail template, its branch, the
+// session table and the submissions go up in one copy, one launch gives a lane to
+// each submission.  The buffers are job_verify_impl's (a context runs one call at a
+// time).  Device buffer, in 8-byte units:
+//   tail | branch | sessions | submits | ctl | verdicts | lanes
+// ctl (ctl_u units, zeros, the end of the copy up) and lanes (lane_u units, never
+// copied) are the share set's; bm_pool_verify_gpu asks for none of either.  The
+// pinned host copy has the same layout up to the verdicts' end.
+struct PoolStage {
+    size_t in_u = 0, out_u = 0;       // units before the verdicts (ctl included), units of the verdicts
+    uint32_t* d_out = nullptr;        // the verdicts on the device
+    uint64_t* d_lanes = nullptr;      // lane_u units after them
+    const bm_job_verdict_t* got = nullptr;  // the verdicts' place in the pinned copy
+};
+
+int pool_verify_launch(DeviceCtx& d, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                       const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi, size_t ctl_u,
+                       size_t lane_u, PoolStage& st) {
     if (!g_pool_verify) return BM_EINTERNAL;
-    DeviceCtx& d = ctx->devs[0];
-    BM_HIP(hipSetDevice(d.id));
     PoolVerifyArgs A;
     std::vector<uint32_t> tail, branch;
     host::pool_verify_prepare(job, A, tail, branch);
@@ -202,17 +213,16 @@ int pool_verify_impl(bm_ctx* ctx, const bm_job_t* job, const bm_pool_session_t* 
     A.nsessions = (uint32_t)nsessions;
     A.ntime_lo = ntime_lo;
     A.ntime_hi = ntime_hi;
-    // device buffer, in 8-byte units: tail | branch | sessions | submits | verdicts.  An empty table is
-    // staged as one zero session: a lane whose index is out of range reads entry 0 and stores INVALID
+    // An empty table is staged as one zero session: a lane whose index is out of range reads entry 0 and
+    // stores INVALID
     const size_t staged = nsessions ? nsessions : 1;
     const size_t tail_u = tail.size() / 2, branch_u = branch.size() / 2;
     const size_t ses_u = staged * sizeof(bm_pool_session_t) / 8, sub_u = n * sizeof(bm_pool_submit_t) / 8;
-    const size_t in_u = tail_u + branch_u + ses_u + sub_u;
+    const size_t in_u = tail_u + branch_u + ses_u + sub_u + ctl_u;
     const size_t out_u = n * sizeof(bm_job_verdict_t) / 8;
     BM_TRY(grow(d, d.h_verify, d.hverify_cap, in_u + out_u, sizeof(uint64_t), true));
-    BM_TRY(grow(d, d.d_verify, d.verify_cap, in_u + out_u));
+    BM_TRY(grow(d, d.d_verify, d.verify_cap, in_u + out_u + lane_u));
     uint64_t* stage = d.h_verify;
-    const bm_job_verdict_t* got = reinterpret_cast<const bm_job_verdict_t*>(d.h_verify + in_u);
     std::memcpy(stage, tail.data(), 8 * tail_u);
     if (branch_u) std::memcpy(stage + tail_u, branch.data(), 8 * branch_u);
     if (nsessions)
@@ -220,6 +230,7 @@ int pool_verify_impl(bm_ctx* ctx, const bm_job_t* job, const bm_pool_session_t* 
     else
         std::memset(stage + tail_u + branch_u, 0, 8 * ses_u);
     std::memcpy(stage + tail_u + branch_u + ses_u, submits, 8 * sub_u);
+    if (ctl_u) std::memset(stage + in_u - ctl_u, 0, 8 * ctl_u);
     BM_HIP(hipMemcpyAsync(d.d_verify, stage, 8 * in_u, hipMemcpyHostToDevice, d.stream));
     const uint32_t* d_tail = reinterpret_cast<const uint32_t*>(d.d_verify);
     const uint32_t* d_branch = reinterpret_cast<const uint32_t*>(d.d_verify + tail_u);
@@ -229,22 +240,195 @@ int pool_verify_impl(bm_ctx* ctx, const bm_job_t* job, const bm_pool_session_t* 
     const uint32_t grid = (uint32_t)((n + 63) / 64);
     void* args[] = {&A, &d_tail, &d_branch, &d_ses, &d_sub, &d_out};
     BM_HIP(hipLaunchKernel(g_pool_verify, dim3(grid), dim3(64), args, 0, d.stream));
-    BM_HIP(hipMemcpyAsync(d.h_verify + in_u, d_out, 8 * out_u, hipMemcpyDeviceToHost, d.stream));
-    BM_HIP(hipStreamSynchronize(d.stream));
-    // the tripwire: the ends of the batch and every claimed block, by the CPU path
+    st.in_u = in_u;
+    st.out_u = out_u;
+    st.d_out = d_out;
+    st.d_lanes = d.d_verify + in_u + out_u;
+    st.got = reinterpret_cast<const bm_job_verdict_t*>(d.h_verify + in_u);
+    return BM_OK;
+}
+
+// The tripwire: the ends of the batch and every claimed block, by the CPU path.  The
+// status bits of `ignore` are not the verifier's and do not count.
+int pool_verify_tripwire(const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                         const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                         const bm_job_verdict_t* got, uint32_t ignore) {
     uint8_t bt[32];
     const uint8_t* block_target = host::target_from_bits(job->nbits, bt) ? bt : nullptr;
     for (size_t i = 0; i < n; ++i) {
         if (i != 0 && i != n - 1 && !(got[i].status & BM_SUBMIT_BLOCK)) continue;
-        bm_job_verdict_t want;
+        bm_job_verdict_t want, have = got[i];
+        have.status &= ~ignore;
         host::pool_verify_one(job, sessions, nsessions, block_target, ntime_lo, ntime_hi, submits[i], want);
-        if (std::memcmp(&want, &got[i], sizeof want) != 0) return BM_EINTERNAL;
+        if (std::memcmp(&want, &have, sizeof want) != 0) return BM_EINTERNAL;
     }
+    return BM_OK;
+}
+
+// bm_pool_verify_gpu on the first device, the shape of job_verify_impl: one copy up,
+// one launch, the verdicts back in one copy.  The caller's arrays are written last.
+int pool_verify_impl(bm_ctx* ctx, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                     const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                     bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out) {
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    PoolStage st;
+    BM_TRY(pool_verify_launch(d, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, 0, 0, st));
+    BM_HIP(hipMemcpyAsync(d.h_verify + st.in_u, st.d_out, 8 * st.out_u, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    BM_TRY(pool_verify_tripwire(job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, st.got, 0));
     bm_pool_verify_result_t r;
-    host::pool_verify_count(got, n, r);
-    std::memcpy(verdicts, got, n * sizeof(bm_job_verdict_t));
+    host::pool_verify_count(st.got, n, r);
+    std::memcpy(verdicts, st.got, n * sizeof(bm_job_verdict_t));
     *out = r;
     return BM_OK;
+}
+
+// ---- the share set on a device (bm_share_set_host.hpp, bm_share_set.hpp) ----
+// The four kernels, registered by bm_share_set_inst.hip at load time
+const void* g_share_insert = nullptr;
+const void* g_share_resolve = nullptr;
+const void* g_share_commit = nullptr;
+const void* g_share_rollback = nullptr;
+
+// Winners store EMPTY again: the table is what it was before the call's insert.
+int share_set_rollback(DeviceCtx& d, const ShareSetArgs& S, uint32_t* d_slots, const uint32_t* lane_slot,
+                       const uint32_t* lane_rank) {
+    ShareSetArgs A = S;
+    void* args[] = {&A, &d_slots, &lane_slot, &lane_rank};
+    BM_HIP(hipLaunchKernel(g_share_rollback, dim3((S.n + 63) / 64), dim3(kShareSetThreads), args, 0, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    return BM_OK;
+}
+
+// bm_share_set_verify on a device set: bm_pool_verify_gpu's stage and launch, then the
+// insert and the resolve on the same stream, one copy back (the two control words
+// and the verdicts, adjacent on the device), and the commit -- or the rollback, when
+// the batch does not fit.  The caller's arrays are written last.  From the insert's
+// launch to the end of the commit or rollback the table holds this call's candidate
+// ids: a failure in between poisons the set until it is cleared.
+int share_set_verify_impl(bm_share_set_t* set, const bm_job_t* job, const bm_pool_session_t* sessions,
+                          size_t nsessions, const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo,
+                          uint32_t ntime_hi, bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
+    if (!g_share_insert || !g_share_resolve || !g_share_commit || !g_share_rollback) return BM_EINTERNAL;
+    if (set->poisoned) return BM_EINTERNAL;
+    DeviceCtx& d = set->ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    static_assert(kShareCtlWords * sizeof(uint32_t) == sizeof(uint64_t), "the control words are one unit");
+    PoolStage st;
+    BM_TRY(pool_verify_launch(d, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, 1, n, st));
+    ShareSetArgs S;
+    S.n = (uint32_t)n;
+    S.nslots = set->nslots;
+    S.count = (uint32_t)set->count;
+    S.capacity = (uint32_t)set->capacity;
+    uint32_t* d_verdicts = st.d_out;
+    uint32_t* d_ctl = st.d_out - kShareCtlWords;
+    uint32_t* lane_slot = reinterpret_cast<uint32_t*>(st.d_lanes);
+    uint32_t* lane_rank = lane_slot + n;
+    const uint32_t* d_keys = set->d_keys;
+    uint32_t* d_slots = set->d_slots;
+    const dim3 grid((uint32_t)((n + 63) / 64)), block(kShareSetThreads);
+    const uint32_t* ctl = reinterpret_cast<const uint32_t*>(st.got) - kShareCtlWords;
+    set->poisoned = true;
+    {
+        void* args[] = {&S, &d_verdicts, &d_keys, &d_slots, &lane_slot, &d_ctl};
+        BM_HIP(hipLaunchKernel(g_share_insert, grid, block, args, 0, d.stream));
+    }
+    {
+        void* args[] = {&S, &d_verdicts, &d_slots, &lane_slot, &lane_rank, &d_ctl};
+        BM_HIP(hipLaunchKernel(g_share_resolve, grid, block, args, 0, d.stream));
+    }
+    BM_HIP(hipMemcpyAsync(d.h_verify + st.in_u - 1, d_ctl, 8 * (1 + st.out_u), hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    const uint32_t fault = ctl[kShareCtlFault];
+    const uint64_t winners = ctl[kShareCtlWinners];
+    bm_share_set_result_t r;
+    host::share_set_count(st.got, n, r);
+    uint64_t eligible = 0;
+    for (size_t i = 0; i < n; ++i) eligible += share_eligible(st.got[i].status) ? 1 : 0;
+    int rc = BM_OK;
+    if (fault & kShareFaultId)
+        rc = BM_EINTERNAL;
+    else if ((fault & kShareFaultFull) || set->count + winners > set->capacity)
+        rc = BM_EFULL;
+    else if (winners + r.duplicates != eligible)  // every eligible lane is a winner or a duplicate
+        rc = BM_EINTERNAL;
+    else
+        rc = pool_verify_tripwire(job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, st.got, BM_SUBMIT_DUPLICATE);
+    if (rc != BM_OK) {
+        BM_TRY(share_set_rollback(d, S, d_slots, lane_slot, lane_rank));
+        set->poisoned = false;
+        return rc;
+    }
+    {
+        uint32_t* keys = set->d_keys;
+        void* args[] = {&S, &d_verdicts, &keys, &d_slots, &lane_slot, &lane_rank};
+        BM_HIP(hipLaunchKernel(g_share_commit, grid, block, args, 0, d.stream));
+    }
+    BM_HIP(hipStreamSynchronize(d.stream));
+    set->poisoned = false;
+    set->count += winners;
+    r.recorded = winners;
+    r.count = set->count;
+    std::memcpy(verdicts, st.got, n * sizeof(bm_job_verdict_t));
+    *out = r;
+    return BM_OK;
+}
+
+int share_set_clear_impl(bm_share_set_t* set) {
+    DeviceCtx& d = set->ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    BM_HIP(hipMemsetAsync(set->d_slots, 0xFF, sizeof(uint32_t) * (size_t)set->nslots, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    set->count = 0;
+    set->poisoned = false;
+    return BM_OK;
+}
+
+int share_set_verify_op(bm_share_set_t* set, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                        const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                        bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
+    DeviceGuard guard;
+    return guarded([&] {
+        return share_set_verify_impl(set, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, verdicts, out);
+    });
+}
+
+int share_set_clear_op(bm_share_set_t* set) {
+    DeviceGuard guard;
+    return share_set_clear_impl(set);
+}
+
+void share_set_destroy_op(bm_share_set_t* set) {
+    DeviceGuard guard;
+    DeviceCtx& d = set->ctx->devs[0];
+    (void)hipSetDevice(d.id);
+    (void)hipStreamSynchronize(d.stream);
+    if (set->d_keys) (void)hipFree(set->d_keys);
+    if (set->d_slots) (void)hipFree(set->d_slots);
+    set->d_keys = set->d_slots = nullptr;
+}
+
+const ShareSetDeviceOps kShareSetOps = {share_set_verify_op, share_set_clear_op, share_set_destroy_op};
+
+// The set's two device arrays, the table empty.  A failed allocation frees what it
+// made and leaves the context as it was.
+int share_set_create_impl(bm_ctx* ctx, bm_share_set_t* set) {
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, sizeof(uint32_t) * kShareKeyWords * set->capacity);
+    if (e == hipSuccess) {
+        set->d_keys = static_cast<uint32_t*>(p);
+        e = hipMalloc(&p, sizeof(uint32_t) * (size_t)set->nslots);
+        if (e == hipSuccess) set->d_slots = static_cast<uint32_t*>(p);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? BM_ENOMEM : BM_EHIP;
+    }
+    return share_set_clear_impl(set);
 }
 
 }  // namespace
@@ -269,6 +453,32 @@ int bm_pool_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const bm_pool_session
     return bm::guarded([&] {
         return bm::pool_verify_impl(ctx, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, verdicts, out);
     });
+}
+
+void bm_register_share_set_kernels(const void* insert, const void* resolve, const void* commit, const void* rollback) {
+    bm::g_share_insert = insert;
+    bm::g_share_resolve = resolve;
+    bm::g_share_commit = commit;
+    bm::g_share_rollback = rollback;
+}
+
+int bm_share_set_create(bm_ctx_t* ctx, size_t capacity, bm_share_set_t** out) {
+    if (!ctx || !out || capacity == 0 || capacity > BM_MAX_SHARE_SET) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    bm_share_set_t* set = new (std::nothrow) bm_share_set;
+    if (!set) return BM_ENOMEM;
+    set->capacity = capacity;
+    set->nslots = bm::share_set_slots(capacity);
+    set->ctx = ctx;
+    set->ops = &bm::kShareSetOps;
+    bm::DeviceGuard guard;
+    const int rc = bm::share_set_create_impl(ctx, set);
+    if (rc != BM_OK) {
+        bm_share_set_destroy(set);
+        return rc;
+    }
+    *out = set;
+    return BM_OK;
 }
 
 void bm_register_job_verify_kernel(const void* fn) { bm::g_job_verify = fn; }

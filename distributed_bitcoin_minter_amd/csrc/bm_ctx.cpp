@@ -288,6 +288,7 @@ const char* bm_strerror(int status) {
         case BM_EINTERNAL: return "internal error";
         case BM_EPEER: return "another rank of the group failed";
         case BM_ETIMEDOUT: return "the group did not answer within the peer timeout";
+        case BM_EFULL: return "the share set is full";
         default: return "unknown status";
     }
 }

@@ -7,7 +7,8 @@
 //                  a host wrapper that launches the reduction, and the entry points
 //                  built on them (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu), and
 //                  bm_job_verify_gpu over job_verify_kernel (bm_job_verify_inst.hip) and
-//                  bm_pool_verify_gpu over pool_verify_kernel (bm_pool_verify_inst.hip)
+//                  bm_pool_verify_gpu over pool_verify_kernel (bm_pool_verify_inst.hip), and
+//                  the device side of bm_share_set_verify (bm_share_set_inst.hip)
 // The first three are plain C++ over the HIP host API.  DESIGN.md section 1.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -96,7 +97,8 @@ struct DeviceCtx {
     uint32_t* d_hdr_io = nullptr;  // bm_header_hash_gpu: n nonces, then 8 digest words per nonce
     size_t hdr_cap = 0;
     uint64_t* d_verify = nullptr;  // bm_job_verify_gpu: tail template, branch, n submissions, then n verdicts
-                                   // (bm_pool_verify_gpu: the session table between the branch and the submissions)
+                                   // (bm_pool_verify_gpu: the session table between the branch and the submissions;
+                                   // bm_share_set_verify: two control words before the verdicts, 8 bytes per lane after)
     uint64_t* h_verify = nullptr;  // pinned copy of the same layout: staged for the copy up, target of the copy back
     size_t verify_cap = 0, hverify_cap = 0;  // in 8-byte units
     hipEvent_t ev[2 * kEventPairs] = {};

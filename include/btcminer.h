@@ -52,6 +52,7 @@ extern "C" {
 #define BM_EINTERNAL (-6)/* planner invariant violated (a bug) */
 #define BM_EPEER (-7)    /* rank contexts: another rank of the group failed this call */
 #define BM_ETIMEDOUT (-8)/* rank contexts: the group did not answer within the peer timeout */
+#define BM_EFULL (-9)    /* bm_share_set_verify: the batch's new hashes do not fit the set */
 
 #define BM_MAX_MSG_LEN (1u << 20) /* bytes; LSP payloads are ~1 KB (README:61) */
 
@@ -662,7 +663,7 @@ int bm_job_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const uint8_t target[3
  *   n == 0 succeeds with a zero *out and touches no array (submits and verdicts may
  *     be NULL).  nsessions == 0 with n > 0 is legal (sessions may be NULL then):
  *     every entry is INVALID.
- *   Duplicate detection stays the caller's: a pool needs it across batches anyway.
+ *   Duplicate detection is bm_share_set_verify's, below: this call flags none.
  * BM_EINVAL: n > BM_MAX_JOB_SUBMITS or nsessions > BM_MAX_POOL_SESSIONS; a NULL
  * job or out (or ctx); NULL submits or verdicts with n > 0; NULL sessions with
  * nsessions > 0; extranonce1_len outside 1..8; a job bm_job_header refuses
@@ -678,8 +679,9 @@ int bm_job_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const uint8_t target[3
  * and returns BM_EINTERNAL on any difference: a tripwire, not the result.
  * bm_ctx_last_stats is left as the previous call left it.
  *
- * Out of scope: duplicate detection; vardiff policy; a network Stratum server;
- * several jobs in one call; splitting a batch over devices; rank groups. */
+ * Out of scope: duplicate detection (bm_share_set_verify, below); vardiff policy; a
+ * network Stratum server; several jobs in one call; splitting a batch over devices;
+ * rank groups. */
 #define BM_MAX_POOL_SESSIONS (1u << 20)
 #define BM_SUBMIT_NTIME 8u            /* ntime outside [ntime_lo, ntime_hi]; hashed all the same */
 typedef struct bm_pool_session {
@@ -702,6 +704,89 @@ int bm_pool_verify_cpu(const bm_job_t* job, const bm_pool_session_t* sessions, s
 int bm_pool_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
                        const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
                        bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out);
+
+/* ---- duplicate-share detection: a per-job set of header hashes ------------------
+ * A pool that pays for shares must not pay twice for one.  A bm_share_set_t is an
+ * opaque set of 32-byte header hashes with a fixed `capacity`; by convention it
+ * holds one job (bm_share_set_clear starts the next).  bm_share_set_create makes
+ * it on the first device of ctx, where it lives across calls; bm_share_set_create_cpu
+ * makes it in host memory, with no context: the specification.
+ *
+ * bm_share_set_verify is bm_pool_verify_* plus the set.  It processes the batch as
+ * if one submission at a time, in the caller's order:
+ *   verdicts[i].hash and .status are exactly bm_pool_verify_cpu's for the same
+ *     arguments, but for one more flag.
+ *   A submission is ELIGIBLE when its status has BM_SUBMIT_SHARE or BM_SUBMIT_BLOCK
+ *     and not BM_SUBMIT_INVALID.  BM_SUBMIT_NTIME does not matter: it stays
+ *     advisory.  An ineligible submission never touches the set and is never
+ *     flagged, however often it repeats.
+ *   An eligible submission whose hash is in the set -- from an earlier call, or from
+ *     a lower index of this batch -- gets BM_SUBMIT_DUPLICATE OR-ed into its status;
+ *     its other bits and its hash are unchanged.
+ *   An eligible submission whose hash is not in the set is recorded and not flagged:
+ *     of equal hashes inside one batch exactly the lowest index is the unflagged one.
+ *   The key is the hash, all 256 bits of it, not the tuple: the same work from two
+ *     sessions that share an extranonce1 is a duplicate; the same (extranonce2,
+ *     ntime, nonce, version) under different extranonce1 values is not.
+ *   out: bm_pool_verify_result_t's five counts, then `duplicates` (verdicts with
+ *     BM_SUBMIT_DUPLICATE), `recorded` (hashes this call added) and `count` (the
+ *     set's size after the call).
+ *   All or nothing: if the batch's new distinct hashes do not fit (count + new >
+ *     capacity) the call returns BM_EFULL, `verdicts` and `out` are untouched, the set
+ *     is exactly as before, and a later call behaves as if this one never happened.
+ *   n == 0 is legal and changes nothing (*out: zeros and the set's count).
+ * BM_EINVAL: everything bm_pool_verify_* refuses, a NULL set, and at creation a NULL
+ * out (or ctx), a capacity of 0 or above BM_MAX_SHARE_SET, a rank context with
+ * world > 1.  A device allocation that fails is BM_ENOMEM and leaves the context
+ * usable.  On any failure `verdicts` and `out` are untouched and the set is as before.
+ * Calls on one set are serialized by the caller, as calls on one context are (the
+ * set uses its context's buffers and stream); two sets on one context are
+ * independent.  bm_share_set_destroy(NULL) is fine; a device set is destroyed before
+ * its context.  bm_share_set_clear forgets every hash (a new job);
+ * bm_share_set_count reports the size and the capacity (either pointer may be NULL).
+ *
+ * The device set is an insert-only open-addressing table of 32-bit entry ids over a
+ * key array keys[capacity] of 32-byte hashes.  The slot count is the smallest power
+ * of two that is at least 2 * capacity and at least 16, and a hash's HOME SLOT is
+ *     (its least significant 32 bits: hash[28..31] as a big-endian integer) mod slots
+ * -- the least significant end, because an accepted share's most significant words
+ * are zero by construction.  Probing is linear, wraps at the table's end and visits
+ * at most `slots` slots; equality is over all 256 bits, never a tag.  One call is
+ * bm_pool_verify_gpu's stage and pool_verify_kernel, then on the same stream
+ *   share_insert_kernel   eligible lanes claim a slot with atomicCAS(EMPTY, 0x80000000
+ *                         | i) or, meeting their own key, atomicMin their id into it:
+ *                         the lowest index wins, or the persistent entry stays;
+ *   share_resolve_kernel  a later launch: a lane whose slot holds its id is a winner,
+ *                         any other eligible lane ORs in BM_SUBMIT_DUPLICATE; the
+ *                         winners are counted with one atomicAdd per wave;
+ *   one copy back (the verdicts and two control words), then
+ *   share_commit_kernel   winners copy their key to keys[count + rank] and store that
+ *                         id in their slot -- or share_rollback_kernel: winners store
+ *                         EMPTY, which restores the table exactly (BM_EFULL).
+ * No lane spins, retries or waits on another; the verdict bytes depend only on the
+ * arguments and the set's contents.  The host tripwire is bm_pool_verify_gpu's, with
+ * BM_SUBMIT_DUPLICATE masked off.  bm_ctx_last_stats is left alone.
+ *
+ * Out of scope: vardiff policy; a network Stratum server; several jobs in one set or
+ * one call; expiring or removing entries; sets over several devices or rank groups. */
+#define BM_SUBMIT_DUPLICATE 16u       /* an eligible hash the set already held (bm_share_set_verify only) */
+#define BM_MAX_SHARE_SET (1u << 24)
+typedef struct bm_share_set bm_share_set_t;
+typedef struct bm_share_set_result {
+    uint64_t n, shares, blocks, invalid, ntime; /* as bm_pool_verify_result_t */
+    uint64_t duplicates;              /* verdicts with BM_SUBMIT_DUPLICATE */
+    uint64_t recorded;                /* hashes this call added */
+    uint64_t count;                   /* the set's size after the call */
+} bm_share_set_result_t;              /* 64 bytes */
+
+int bm_share_set_create(bm_ctx_t* ctx, size_t capacity, bm_share_set_t** out);
+int bm_share_set_create_cpu(size_t capacity, bm_share_set_t** out);
+void bm_share_set_destroy(bm_share_set_t* set);
+int bm_share_set_clear(bm_share_set_t* set);
+int bm_share_set_count(const bm_share_set_t* set, uint64_t* count, uint64_t* capacity);
+int bm_share_set_verify(bm_share_set_t* set, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
+                        const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
+                        bm_job_verdict_t* verdicts, bm_share_set_result_t* out);
 
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */

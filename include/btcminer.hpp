@@ -359,6 +359,66 @@ class Context {
     bm_ctx_t* ctx_ = nullptr;
 };
 
+// A bm_share_set_t: the set of header hashes behind duplicate-share detection, by
+// convention one job's.  ShareSet(ctx, capacity) lives on the first device of ctx,
+// across calls, and is destroyed before ctx; ShareSet::cpu(capacity) lives in host
+// memory and needs no GPU: the specification.  Move-only.
+class ShareSet {
+   public:
+    ShareSet(Context& ctx, size_t capacity) { check(bm_share_set_create(ctx.get(), capacity, &set_), "bm_share_set_create"); }
+    static ShareSet cpu(size_t capacity) {
+        ShareSet s;
+        check(bm_share_set_create_cpu(capacity, &s.set_), "bm_share_set_create_cpu");
+        return s;
+    }
+    ShareSet(const ShareSet&) = delete;
+    ShareSet& operator=(const ShareSet&) = delete;
+    ShareSet(ShareSet&& o) noexcept : set_(o.set_) { o.set_ = nullptr; }
+    ShareSet& operator=(ShareSet&& o) noexcept {
+        if (this != &o) {
+            bm_share_set_destroy(set_);
+            set_ = o.set_;
+            o.set_ = nullptr;
+        }
+        return *this;
+    }
+    ~ShareSet() { bm_share_set_destroy(set_); }
+
+    // Context::verify_pool_submits plus the set: an eligible submission (SHARE or
+    // BLOCK, not INVALID) whose hash the set holds carries BM_SUBMIT_DUPLICATE, any
+    // other eligible one is recorded.  All or nothing: Error with status BM_EFULL
+    // when the batch's new hashes do not fit, `verdicts` and the set as before.
+    bm_share_set_result_t verify(const Job& job, const std::vector<bm_pool_session_t>& sessions,
+                                 const bm_pool_submit_t* submits, size_t n, std::vector<bm_job_verdict_t>& verdicts,
+                                 uint32_t ntime_lo = 0, uint32_t ntime_hi = 0xFFFFFFFFu) {
+        if (job.branch.size() % 32 != 0) throw Error(BM_EINVAL, "ShareSet::verify");
+        const bm_job_t j = job.view();
+        bm_share_set_result_t r;
+        std::vector<bm_job_verdict_t> buf(n);
+        check(bm_share_set_verify(set_, &j, sessions.empty() ? nullptr : sessions.data(), sessions.size(), submits, n,
+                                  ntime_lo, ntime_hi, n ? buf.data() : nullptr, &r),
+              "bm_share_set_verify");
+        verdicts = std::move(buf);
+        return r;
+    }
+    void clear() { check(bm_share_set_clear(set_), "bm_share_set_clear"); }  // a new job
+    uint64_t count() const {
+        uint64_t n = 0;
+        check(bm_share_set_count(set_, &n, nullptr), "bm_share_set_count");
+        return n;
+    }
+    uint64_t capacity() const {
+        uint64_t n = 0;
+        check(bm_share_set_count(set_, nullptr, &n), "bm_share_set_count");
+        return n;
+    }
+    bm_share_set_t* get() const { return set_; }
+
+   private:
+    ShareSet() = default;
+    bm_share_set_t* set_ = nullptr;
+};
+
 }  // namespace btcminer
 
 namespace bitcoin {

@@ -1,0 +1,26 @@
+"""The share set's host code under sanitizers (no GPU): tools/share_set_check.cpp,
+a stand-alone program over csrc/bm_share_set.cpp and csrc/bm_job.cpp, built with
+ASan and UBSan and run on the CPU."""
+import os
+import subprocess
+import tempfile
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "distributed_bitcoin_minter_amd", "csrc")
+
+
+def test_share_set_host_code_under_sanitizers():
+    """The CPU set on exactly-sized heap buffers for the job's parts, `sessions`,
+    `submits` and `verdicts`, against bm_pool_verify_cpu plus a std::set; BM_EFULL
+    and its rollback; the argument checks with canaries; creation, clear, count."""
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "share_set_check")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
+                               "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                               "-I", CSRC, "-I", os.path.join(ROOT, "include"),
+                               os.path.join(ROOT, "tools", "share_set_check.cpp"), os.path.join(CSRC, "bm_share_set.cpp"),
+                               os.path.join(CSRC, "bm_job.cpp"), "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert r.stdout.strip().endswith("share set check ok")
