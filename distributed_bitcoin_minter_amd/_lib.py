@@ -242,6 +242,20 @@ class ShareSetResult(ctypes.Structure):
                 ("duplicates", c_u64), ("recorded", c_u64), ("count", c_u64)]
 
 
+BM_MAX_POOL_JOBS = 64
+
+
+class PoolJobStruct(ctypes.Structure):
+    """bm_pool_job_t: a job as the pool calls read it, and its ntime window."""
+    _fields_ = [("job", JobStruct), ("ntime_lo", c_u32), ("ntime_hi", c_u32)]
+
+
+class JobsSubmit(ctypes.Structure):
+    """bm_jobs_submit_t: PoolSubmit with the index of the submission's job."""
+    _fields_ = [("extranonce2", c_u64), ("ntime", c_u32), ("nonce", c_u32), ("version", c_u32), ("session", c_u32),
+                ("job", c_u32), ("reserved", c_u32)]
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -340,6 +354,12 @@ def _open(path):
                                 c_u32, c_u32, P(JobVerdict), P(PoolVerifyResult)], ctypes.c_int),
         "bm_pool_verify_gpu": ([vp, P(JobStruct), P(PoolSessionStruct), ctypes.c_size_t, P(PoolSubmit),
                                 ctypes.c_size_t, c_u32, c_u32, P(JobVerdict), P(PoolVerifyResult)], ctypes.c_int),
+        "bm_jobs_verify_cpu": ([P(PoolJobStruct), ctypes.c_size_t, P(PoolSessionStruct), ctypes.c_size_t, P(JobsSubmit),
+                                ctypes.c_size_t, P(JobVerdict), P(PoolVerifyResult)], ctypes.c_int),
+        "bm_jobs_verify_gpu": ([vp, P(PoolJobStruct), ctypes.c_size_t, P(PoolSessionStruct), ctypes.c_size_t,
+                                P(JobsSubmit), ctypes.c_size_t, P(JobVerdict), P(PoolVerifyResult)], ctypes.c_int),
+        "bm_share_set_verify_jobs": ([vp, P(PoolJobStruct), ctypes.c_size_t, P(PoolSessionStruct), ctypes.c_size_t,
+                                      P(JobsSubmit), ctypes.c_size_t, P(JobVerdict), P(ShareSetResult)], ctypes.c_int),
         "bm_share_set_create": ([vp, ctypes.c_size_t, P(vp)], ctypes.c_int),
         "bm_share_set_create_cpu": ([ctypes.c_size_t, P(vp)], ctypes.c_int),
         "bm_share_set_destroy": ([vp], None),
@@ -728,9 +748,115 @@ def verify_pool_submits_cpu(job, sessions, submits, ntime_lo: int = 0, ntime_hi:
     return _pool_verify(load().bm_pool_verify_cpu, "bm_pool_verify_cpu", job, sessions, submits, ntime_lo, ntime_hi)
 
 
+class PoolJob:
+    """One live job of a pool (bm_pool_job_t): a Job, read as the pool calls read
+    it (its extranonce1 gives the size only), and its own ntime window, inclusive."""
+    __slots__ = ("job", "ntime_lo", "ntime_hi")
+
+    def __init__(self, job, ntime_lo: int = 0, ntime_hi: int = U32_MAX):
+        if not isinstance(job, Job):
+            raise ValueError("job must be a Job")
+        if not 1 <= len(job.extranonce1) <= 8:
+            raise ValueError(f"a pool job's extranonce1 gives the size of every session's: 1..8 bytes, got {len(job.extranonce1)}")
+        self.job, self.ntime_lo, self.ntime_hi = job, _u32(ntime_lo, "ntime_lo"), _u32(ntime_hi, "ntime_hi")
+
+    def __repr__(self):
+        return f"PoolJob({self.job.job_id!r}, {self.ntime_lo}, {self.ntime_hi})"
+
+
+def parse_jobs_submit(params, jobs_by_id, index, mask: int = BIP320_MASK):
+    """parse_pool_submit over several live jobs: params[1], the job id, picks the
+    job through jobs_by_id, a mapping id -> (index into the call's jobs, Job); the
+    result carries that index as "job" beside parse_pool_submit's fields.  Raises
+    parse_pool_submit's reasons -- but for "job-id" -- and ValueError("job: ...")
+    for an id the mapping does not hold."""
+    if not isinstance(params, (list, tuple)) or len(params) not in (5, 6):
+        raise ValueError("malformed: mining.submit has 5 or 6 params")
+    job_id = params[1]
+    if not isinstance(job_id, str) or job_id not in jobs_by_id:
+        raise ValueError(f"job: no live job {job_id!r}")
+    j, job = jobs_by_id[job_id]
+    return dict(parse_pool_submit(params, job, index, mask), job=j)
+
+
+def _jobs_array(jobs):
+    """(a (PoolJobStruct * n) array, the PoolJob rows that keep its buffers alive)
+    from an iterable of PoolJob, Job (no window) or (job, ntime_lo, ntime_hi)."""
+    rows = [j if isinstance(j, PoolJob) else PoolJob(j) if isinstance(j, Job) else PoolJob(*j) for j in jobs]
+    if len(rows) > BM_MAX_POOL_JOBS:
+        raise ValueError(f"at most {BM_MAX_POOL_JOBS} jobs per call, got {len(rows)}")
+    arr = (PoolJobStruct * len(rows))()
+    for a, r in zip(arr, rows):
+        ctypes.memmove(ctypes.byref(a.job), ctypes.byref(r.job.struct), ctypes.sizeof(JobStruct))
+        a.ntime_lo, a.ntime_hi = r.ntime_lo, r.ntime_hi
+    return arr, rows
+
+
+def _jobs_session_array(sessions, size):
+    """A (PoolSessionStruct * n) array from one (used as it is) or from an iterable
+    of PoolSession or (extranonce1, target) pairs, each extranonce1 at least size
+    bytes (the longest any of the call's jobs reads: a job reads its first
+    extranonce1_len bytes)."""
+    if isinstance(sessions, ctypes.Array) and sessions._type_ is PoolSessionStruct:
+        return sessions
+    rows = [s if isinstance(s, PoolSession) else PoolSession(*s) for s in sessions]
+    arr = (PoolSessionStruct * len(rows))()
+    for a, s in zip(arr, rows):
+        if len(s.extranonce1) < size:
+            raise ValueError(f"every session's extranonce1 is at least {size} bytes (the jobs' longest), got {s.extranonce1!r}")
+        ctypes.memmove(a.extranonce1, s.extranonce1, len(s.extranonce1))
+        ctypes.memmove(a.target, s.target.to_bytes(32, "big"), 32)
+    return arr
+
+
+def _jobs_submit_array(submits):
+    """A (JobsSubmit * n) array from one (used as it is) or from an iterable of
+    dicts (extranonce2, ntime, nonce, version, session, job: parse_jobs_submit's)
+    or (extranonce2, ntime, nonce, version, session, job) tuples."""
+    if isinstance(submits, ctypes.Array) and submits._type_ is JobsSubmit:
+        return submits
+    keys = ("extranonce2", "ntime", "nonce", "version", "session", "job")
+    rows = []
+    for s in submits:
+        row = tuple(s[k] for k in keys) if isinstance(s, dict) else tuple(s)
+        if len(row) != 6:
+            raise ValueError(f"a submission over several jobs is (extranonce2, ntime, nonce, version, session, job), got {s!r}")
+        if not isinstance(row[0], int) or isinstance(row[0], bool) or not 0 <= row[0] <= U64_MAX:
+            raise ValueError(f"extranonce2 must be in 0..2^64-1, got {row[0]!r}")
+        for v, what in zip(row[1:], keys[1:]):
+            _u32(v, what)
+        rows.append(row)
+    arr = (JobsSubmit * len(rows))()
+    for a, row in zip(arr, rows):
+        a.extranonce2, a.ntime, a.nonce, a.version, a.session, a.job = row
+    return arr
+
+
+def _jobs_verify(call, what, jobs, sessions, submits, result=None):
+    jarr, rows = _jobs_array(jobs)
+    ses = _jobs_session_array(sessions, max((len(r.job.extranonce1) for r in rows), default=0))
+    arr = _jobs_submit_array(submits)
+    if len(arr) > BM_MAX_JOB_SUBMITS:
+        raise ValueError(f"at most {BM_MAX_JOB_SUBMITS} submissions per call, got {len(arr)}")
+    if len(ses) > BM_MAX_POOL_SESSIONS:
+        raise ValueError(f"at most {BM_MAX_POOL_SESSIONS} sessions per call, got {len(ses)}")
+    verdicts = (JobVerdict * len(arr))()
+    r = (result or PoolVerifyResult)()
+    check(call(jarr if len(jarr) else None, len(jarr), ses if len(ses) else None, len(ses), arr if len(arr) else None,
+               len(arr), verdicts if len(arr) else None, ctypes.byref(r)), what)
+    return verdicts, r
+
+
+def verify_jobs_submits_cpu(jobs, sessions, submits):
+    """Context.verify_jobs_submits without a GPU or a context (bm_jobs_verify_cpu,
+    pure CPU): the specification of the GPU entry, byte-identical to it."""
+    return _jobs_verify(load().bm_jobs_verify_cpu, "bm_jobs_verify_cpu", jobs, sessions, submits)
+
+
 class ShareSet:
     """A bm_share_set_t: the set of header hashes behind duplicate-share detection,
-    by convention one job's.  ShareSet(ctx, capacity) lives on the first device of
+    cleared by the caller when its jobs retire (the key is the header hash, which
+    separates jobs: one set may hold several jobs' shares).  ShareSet(ctx, capacity) lives on the first device of
     ctx, across calls, and is closed before ctx; ShareSet.cpu(capacity) lives in
     host memory and needs no GPU: the specification.  Not thread-safe, and a device
     set shares its context's buffers: one call at a time per context."""
@@ -793,7 +919,7 @@ class ShareSet:
         return self._sizes()[1]
 
     def clear(self):
-        """Forget every hash: a new job."""
+        """Forget every hash: the set's jobs have retired (a new block height)."""
         check(self._lib.bm_share_set_clear(self.handle), "bm_share_set_clear")
 
     def verify(self, job, sessions, submits, ntime_lo: int = 0, ntime_hi: int = (1 << 32) - 1):
@@ -805,6 +931,14 @@ class ShareSet:
         not fit, and the set is as before."""
         return _pool_verify(lambda *a: self._lib.bm_share_set_verify(self.handle, *a), "bm_share_set_verify", job,
                             sessions, submits, ntime_lo, ntime_hi, ShareSetResult)
+
+    def verify_jobs(self, jobs, sessions, submits):
+        """Context.verify_jobs_submits plus the set (bm_share_set_verify_jobs) ->
+        (verdicts, ShareSetResult), as verify: the key is the header hash, so the
+        set may be fed by verify and verify_jobs alternately, and the same tuple
+        under two jobs[] entries of identical content is a duplicate."""
+        return _jobs_verify(lambda *a: self._lib.bm_share_set_verify_jobs(self.handle, *a), "bm_share_set_verify_jobs",
+                            jobs, sessions, submits, ShareSetResult)
 
 
 def _header_bytes(header) -> bytes:
@@ -1115,6 +1249,20 @@ class Context:
         session index past the table; result is a PoolVerifyResult."""
         return _pool_verify(lambda *a: self._lib.bm_pool_verify_gpu(self.handle, *a), "bm_pool_verify_gpu", job,
                             sessions, submits, ntime_lo, ntime_hi)
+
+    def verify_jobs_submits(self, jobs, sessions, submits):
+        """The submissions of several live jobs in one call, one GPU lane per
+        submission (bm_jobs_verify_gpu) -> (verdicts, result).  jobs: up to 64
+        PoolJob (a Job and its own ntime window; a bare Job has no window);
+        sessions: as verify_pool_submits takes them, shared by all jobs, each
+        extranonce1 at least as long as the longest the jobs state (a job reads
+        its first bytes); submits: a (JobsSubmit * n) array, or an iterable of
+        dicts with extranonce2, ntime, nonce, version, session and job
+        (parse_jobs_submit's answer) or of such 6-tuples.  verdicts[i] is
+        verify_pool_submits' for submission i under its job and that job's
+        window, in the caller's order; a job index past the table is_invalid."""
+        return _jobs_verify(lambda *a: self._lib.bm_jobs_verify_gpu(self.handle, *a), "bm_jobs_verify_gpu", jobs,
+                            sessions, submits)
 
     def search_header_hits(self, header: bytes, nonce_lo: int = 0, nonce_hi: int = U32_MAX, target=U256_MAX,
                            cap: int = 4096):

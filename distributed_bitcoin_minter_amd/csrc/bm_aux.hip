@@ -2,8 +2,9 @@
 // kernels of bm_aux_kernels.hpp, the host wrapper the searches launch the
 // second-pass reduction through, and the entry points outside the search
 // path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu, and bm_job_verify_gpu,
-// bm_pool_verify_gpu and the device side of bm_share_set_verify, whose kernels have
-// units of their own, bm_job_verify_inst.hip, bm_pool_verify_inst.hip and
+// bm_pool_verify_gpu, bm_jobs_verify_gpu and the device side of bm_share_set_verify
+// and bm_share_set_verify_jobs, whose kernels have units of their own,
+// bm_job_verify_inst.hip, bm_pool_verify_inst.hip, bm_jobs_verify_inst.hip and
 // bm_share_set_inst.hip).  See
 // bm_runtime.hpp for the layout of the host runtime.
 #include <hip/hip_runtime.h>
@@ -284,6 +285,101 @@ int pool_verify_impl(bm_ctx* ctx, const bm_job_t* job, const bm_pool_session_t* 
     return BM_OK;
 }
 
+// jobs_verify_kernel, registered by bm_jobs_verify_inst.hip at load time
+const void* g_jobs_verify = nullptr;
+
+// What bm_jobs_verify_gpu and bm_share_set_verify_jobs share: the grouping, the stage
+// and the launch of jobs_verify_kernel.  The buffers are job_verify_impl's.  Device
+// buffer, in 8-byte units:
+//   descriptors | words (all tails, all branches) | sessions | staged submits | block table | ctl | verdicts | lanes
+// with ctl and lanes as in pool_verify_launch, and the verdicts and what follows them
+// where PoolStage says, so the share set's kernels take them unchanged.  The counting
+// sort's scatter is the copy of the submissions into the pinned buffer; plan and
+// *staged (the pinned copy of the staged records) stay valid for the tripwire.
+int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
+                       size_t nsessions, const bm_jobs_submit_t* submits, size_t n, size_t ctl_u, size_t lane_u,
+                       PoolStage& st, host::JobsPlan& plan, const bm_jobs_submit_t** staged) {
+    if (!g_jobs_verify) return BM_EINTERNAL;
+    std::vector<JobsVerifyDesc> desc;
+    std::vector<uint32_t> words;
+    host::jobs_verify_prepare(jobs, njobs, desc, words);
+    host::jobs_plan(submits, n, njobs, plan);
+    // An empty job table is staged as one zero descriptor and an empty session table as one zero session, so
+    // every array on the device has an entry; no lane reads either
+    const size_t ses_staged = nsessions ? nsessions : 1, desc_staged = njobs ? njobs : 1;
+    const size_t desc_u = desc_staged * sizeof(JobsVerifyDesc) / 8, words_u = words.size() / 2;
+    const size_t ses_u = ses_staged * sizeof(bm_pool_session_t) / 8, sub_u = n * sizeof(bm_jobs_submit_t) / 8;
+    const size_t blk_u = plan.blocks.size() * sizeof(JobsVerifyBlock) / 8;
+    const size_t in_u = desc_u + words_u + ses_u + sub_u + blk_u + ctl_u;
+    const size_t out_u = n * sizeof(bm_job_verdict_t) / 8;
+    BM_TRY(grow(d, d.h_verify, d.hverify_cap, in_u + out_u, sizeof(uint64_t), true));
+    BM_TRY(grow(d, d.d_verify, d.verify_cap, in_u + out_u + lane_u));
+    uint64_t* stage = d.h_verify;
+    size_t at = 0;
+    const size_t desc_at = at;
+    if (njobs)
+        std::memcpy(stage + at, desc.data(), 8 * desc_u);
+    else
+        std::memset(stage + at, 0, 8 * desc_u);
+    at += desc_u;
+    const size_t words_at = at;
+    if (words_u) std::memcpy(stage + at, words.data(), 8 * words_u);
+    at += words_u;
+    const size_t ses_at = at;
+    if (nsessions)
+        std::memcpy(stage + at, sessions, 8 * ses_u);
+    else
+        std::memset(stage + at, 0, 8 * ses_u);
+    at += ses_u;
+    const size_t sub_at = at;
+    bm_jobs_submit_t* h_staged = reinterpret_cast<bm_jobs_submit_t*>(stage + at);
+    host::jobs_stage(submits, n, njobs, plan, h_staged);
+    at += sub_u;
+    const size_t blk_at = at;
+    std::memcpy(stage + at, plan.blocks.data(), 8 * blk_u);
+    at += blk_u;
+    if (ctl_u) std::memset(stage + at, 0, 8 * ctl_u);
+    BM_HIP(hipMemcpyAsync(d.d_verify, stage, 8 * in_u, hipMemcpyHostToDevice, d.stream));
+    const JobsVerifyDesc* d_desc = reinterpret_cast<const JobsVerifyDesc*>(d.d_verify + desc_at);
+    const uint32_t* d_words = reinterpret_cast<const uint32_t*>(d.d_verify + words_at);
+    const uint32_t* d_ses = reinterpret_cast<const uint32_t*>(d.d_verify + ses_at);
+    uint32_t nses = (uint32_t)nsessions;
+    const bm_jobs_submit_t* d_sub = reinterpret_cast<const bm_jobs_submit_t*>(d.d_verify + sub_at);
+    const JobsVerifyBlock* d_blk = reinterpret_cast<const JobsVerifyBlock*>(d.d_verify + blk_at);
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(d.d_verify + in_u);
+    void* args[] = {&d_desc, &d_words, &d_ses, &nses, &d_sub, &d_blk, &d_out};
+    BM_HIP(hipLaunchKernel(g_jobs_verify, dim3((uint32_t)plan.blocks.size()), dim3(kJobsVerifyThreads), args, 0,
+                           d.stream));
+    st.in_u = in_u;
+    st.out_u = out_u;
+    st.d_out = d_out;
+    st.d_lanes = d.d_verify + in_u + out_u;
+    st.got = reinterpret_cast<const bm_job_verdict_t*>(d.h_verify + in_u);
+    *staged = h_staged;
+    return BM_OK;
+}
+
+// bm_jobs_verify_gpu on the first device, the shape of pool_verify_impl: one copy up,
+// one launch, the verdicts back in one copy.  The caller's arrays are written last.
+int jobs_verify_impl(bm_ctx* ctx, const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
+                     size_t nsessions, const bm_jobs_submit_t* submits, size_t n, bm_job_verdict_t* verdicts,
+                     bm_pool_verify_result_t* out) {
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    PoolStage st;
+    host::JobsPlan plan;
+    const bm_jobs_submit_t* staged = nullptr;
+    BM_TRY(jobs_verify_launch(d, jobs, njobs, sessions, nsessions, submits, n, 0, 0, st, plan, &staged));
+    BM_HIP(hipMemcpyAsync(d.h_verify + st.in_u, st.d_out, 8 * st.out_u, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    BM_TRY(host::jobs_verify_tripwire(jobs, njobs, sessions, nsessions, submits, n, plan, staged, st.got, 0));
+    bm_pool_verify_result_t r;
+    host::pool_verify_count(st.got, n, r);
+    std::memcpy(verdicts, st.got, n * sizeof(bm_job_verdict_t));
+    *out = r;
+    return BM_OK;
+}
+
 // ---- the share set on a device (bm_share_set_host.hpp, bm_share_set.hpp) ----
 // The four kernels, registered by bm_share_set_inst.hip at load time
 const void* g_share_insert = nullptr;
@@ -301,22 +397,25 @@ int share_set_rollback(DeviceCtx& d, const ShareSetArgs& S, uint32_t* d_slots, c
     return BM_OK;
 }
 
-// bm_share_set_verify on a device set: bm_pool_verify_gpu's stage and launch, then the
+// bm_share_set_verify and bm_share_set_verify_jobs on a device set: a verifier's
+// stage and launch (`launch`: bm_pool_verify_gpu's or bm_jobs_verify_gpu's, with one
+// control unit and n lane units), then the
 // insert and the resolve on the same stream, one copy back (the two control words
 // and the verdicts, adjacent on the device), and the commit -- or the rollback, when
-// the batch does not fit.  The caller's arrays are written last.  From the insert's
+// the batch does not fit.  `tripwire` is that verifier's, over the verdicts with
+// BM_SUBMIT_DUPLICATE masked off.  The caller's arrays are written last.  From the insert's
 // launch to the end of the commit or rollback the table holds this call's candidate
 // ids: a failure in between poisons the set until it is cleared.
-int share_set_verify_impl(bm_share_set_t* set, const bm_job_t* job, const bm_pool_session_t* sessions,
-                          size_t nsessions, const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo,
-                          uint32_t ntime_hi, bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
+template <class Launch, class Tripwire>
+int share_set_verify_impl(bm_share_set_t* set, size_t n, Launch&& launch, Tripwire&& tripwire,
+                          bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
     if (!g_share_insert || !g_share_resolve || !g_share_commit || !g_share_rollback) return BM_EINTERNAL;
     if (set->poisoned) return BM_EINTERNAL;
     DeviceCtx& d = set->ctx->devs[0];
     BM_HIP(hipSetDevice(d.id));
     static_assert(kShareCtlWords * sizeof(uint32_t) == sizeof(uint64_t), "the control words are one unit");
     PoolStage st;
-    BM_TRY(pool_verify_launch(d, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, 1, n, st));
+    BM_TRY(launch(d, st));
     ShareSetArgs S;
     S.n = (uint32_t)n;
     S.nslots = set->nslots;
@@ -355,7 +454,7 @@ int share_set_verify_impl(bm_share_set_t* set, const bm_job_t* job, const bm_poo
     else if (winners + r.duplicates != eligible)  // every eligible lane is a winner or a duplicate
         rc = BM_EINTERNAL;
     else
-        rc = pool_verify_tripwire(job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, st.got, BM_SUBMIT_DUPLICATE);
+        rc = tripwire(st.got);
     if (rc != BM_OK) {
         BM_TRY(share_set_rollback(d, S, d_slots, lane_slot, lane_rank));
         set->poisoned = false;
@@ -391,7 +490,36 @@ int share_set_verify_op(bm_share_set_t* set, const bm_job_t* job, const bm_pool_
                         bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
     DeviceGuard guard;
     return guarded([&] {
-        return share_set_verify_impl(set, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, verdicts, out);
+        return share_set_verify_impl(
+            set, n,
+            [&](DeviceCtx& d, PoolStage& st) {
+                return pool_verify_launch(d, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, 1, n, st);
+            },
+            [&](const bm_job_verdict_t* got) {
+                return pool_verify_tripwire(job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, got,
+                                            BM_SUBMIT_DUPLICATE);
+            },
+            verdicts, out);
+    });
+}
+
+int share_set_verify_jobs_op(bm_share_set_t* set, const bm_pool_job_t* jobs, size_t njobs,
+                             const bm_pool_session_t* sessions, size_t nsessions, const bm_jobs_submit_t* submits,
+                             size_t n, bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
+    DeviceGuard guard;
+    return guarded([&] {
+        host::JobsPlan plan;
+        const bm_jobs_submit_t* staged = nullptr;
+        return share_set_verify_impl(
+            set, n,
+            [&](DeviceCtx& d, PoolStage& st) {
+                return jobs_verify_launch(d, jobs, njobs, sessions, nsessions, submits, n, 1, n, st, plan, &staged);
+            },
+            [&](const bm_job_verdict_t* got) {
+                return host::jobs_verify_tripwire(jobs, njobs, sessions, nsessions, submits, n, plan, staged, got,
+                                                  BM_SUBMIT_DUPLICATE);
+            },
+            verdicts, out);
     });
 }
 
@@ -410,7 +538,8 @@ void share_set_destroy_op(bm_share_set_t* set) {
     set->d_keys = set->d_slots = nullptr;
 }
 
-const ShareSetDeviceOps kShareSetOps = {share_set_verify_op, share_set_clear_op, share_set_destroy_op};
+const ShareSetDeviceOps kShareSetOps = {share_set_verify_op, share_set_verify_jobs_op, share_set_clear_op,
+                                        share_set_destroy_op};
 
 // The set's two device arrays, the table empty.  A failed allocation frees what it
 // made and leaves the context as it was.
@@ -452,6 +581,25 @@ int bm_pool_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const bm_pool_session
     bm::DeviceGuard guard;
     return bm::guarded([&] {
         return bm::pool_verify_impl(ctx, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, verdicts, out);
+    });
+}
+
+void bm_register_jobs_verify_kernel(const void* fn) { bm::g_jobs_verify = fn; }
+
+int bm_jobs_verify_gpu(bm_ctx_t* ctx, const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
+                       size_t nsessions, const bm_jobs_submit_t* submits, size_t n, bm_job_verdict_t* verdicts,
+                       bm_pool_verify_result_t* out) {
+    if (!ctx) return BM_EINVAL;
+    const int rc = bm::host::jobs_verify_check(jobs, njobs, sessions, nsessions, submits, n, verdicts, out);
+    if (rc != BM_OK) return rc;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    if (n == 0) {
+        std::memset(out, 0, sizeof *out);
+        return BM_OK;
+    }
+    bm::DeviceGuard guard;
+    return bm::guarded([&] {
+        return bm::jobs_verify_impl(ctx, jobs, njobs, sessions, nsessions, submits, n, verdicts, out);
     });
 }
 

@@ -1,6 +1,6 @@
 // bm_job.cpp -- the pure-CPU entries of the Stratum job layer (include/btcminer.h):
 // bm_job_prevhash_from_stratum, bm_job_header, bm_job_verify_cpu,
-// bm_pool_verify_cpu, bm_target_from_difficulty.  They need no context and no GPU;
+// bm_pool_verify_cpu, bm_jobs_verify_cpu, bm_target_from_difficulty.  They need no context and no GPU;
 // bm_search_job_shares_gpu (bm_search.cpp) builds its headers and
 // bm_job_verify_gpu and bm_pool_verify_gpu (bm_aux.hip) check their device with the same code
 // (bm_job.hpp).  Plain C++: no HIP in here.
@@ -54,6 +54,18 @@ int bm_pool_verify_cpu(const bm_job_t* job, const bm_pool_session_t* sessions, s
     const uint8_t* block_target = bm::host::target_from_bits(job->nbits, bt) ? bt : nullptr;
     for (size_t i = 0; i < n; ++i)
         bm::host::pool_verify_one(job, sessions, nsessions, block_target, ntime_lo, ntime_hi, submits[i], verdicts[i]);
+    bm::host::pool_verify_count(verdicts, n, *out);
+    return BM_OK;
+}
+
+// The specification of bm_jobs_verify_gpu: bm_pool_verify_cpu per submission, with
+// the submission's job and that job's window; a job index past the table is INVALID.
+int bm_jobs_verify_cpu(const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions, size_t nsessions,
+                       const bm_jobs_submit_t* submits, size_t n, bm_job_verdict_t* verdicts,
+                       bm_pool_verify_result_t* out) {
+    const int rc = bm::host::jobs_verify_check(jobs, njobs, sessions, nsessions, submits, n, verdicts, out);
+    if (rc != BM_OK) return rc;
+    for (size_t i = 0; i < n; ++i) bm::host::jobs_verify_one(jobs, njobs, sessions, nsessions, submits[i], verdicts[i]);
     bm::host::pool_verify_count(verdicts, n, *out);
     return BM_OK;
 }

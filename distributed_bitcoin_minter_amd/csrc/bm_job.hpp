@@ -6,11 +6,13 @@
 // bm_job_verify_gpu): one submission's verdict on the CPU, and what
 // job_verify_kernel (bm_job_verify.hpp) takes of a job; the same for one job's
 // submissions from many sessions (bm_pool_verify_cpu, bm_pool_verify_gpu,
-// pool_verify_kernel in bm_pool_verify.hpp).  Shared by the launcher
-// (bm_search.cpp), bm_aux.hip, the pure-CPU entries (bm_job.cpp) and three
-// stand-alone CPU checks (tools/job_check.cpp, tools/verify_check.cpp,
-// tools/pool_verify_check.cpp).  Plain C++: no HIP in here (en2_words and
-// field_words alone are marked for both sides).
+// pool_verify_kernel in bm_pool_verify.hpp), and for the submissions of several
+// jobs (bm_jobs_verify_cpu, bm_jobs_verify_gpu, jobs_verify_kernel in
+// bm_jobs_verify.hpp: the grouping by job, the descriptors, the tripwire).  Shared
+// by the launcher (bm_search.cpp), bm_aux.hip, the pure-CPU entries (bm_job.cpp)
+// and four stand-alone CPU checks (tools/job_check.cpp, tools/verify_check.cpp,
+// tools/pool_verify_check.cpp, tools/jobs_verify_check.cpp).  Plain C++: no HIP in
+// here (en2_words and field_words alone are marked for both sides).
 //
 //   coinbase = coinb1 || extranonce1 || BE(extranonce2, extranonce2_size) || coinb2
 //   root     = sha256d(coinbase); for each branch entry: root = sha256d(root || entry)
@@ -484,6 +486,186 @@ inline void pool_verify_count(const bm_job_verdict_t* verdicts, size_t n, bm_poo
         out.invalid += (st & BM_SUBMIT_INVALID) ? 1 : 0;
         out.ntime += (st & BM_SUBMIT_NTIME) ? 1 : 0;
     }
+}
+
+}  // namespace host
+
+// ---- share verification over several jobs (bm_jobs_verify_cpu / bm_jobs_verify_gpu) ----
+// Several live jobs, one session table: the job is per-submission data too.  What
+// pool_verify_kernel takes by value, jobs_verify_kernel (bm_jobs_verify.hpp) reads
+// from a descriptor table, and the host groups the batch by job so that a 64-lane
+// workgroup holds one job's submissions only: every loop stays wave-uniform.
+
+// One job as jobs_verify_kernel reads it, through scalar loads: PoolVerifyArgs'
+// per-job fields, the window, and where the job's tail and branch start in the
+// words array (all tails, then all branches), in 32-bit words.
+struct JobsVerifyDesc {
+    uint32_t mid[8];
+    uint32_t prev[8];
+    uint32_t btgt[8];
+    uint32_t nbits;
+    uint32_t has_block;
+    uint32_t nb;
+    uint32_t j0;
+    uint32_t boff;
+    uint32_t size1;
+    uint32_t size2;
+    uint32_t depth;
+    uint32_t ntime_lo, ntime_hi;
+    uint32_t tail_off;    // first word of the tail (16 * nb words)
+    uint32_t branch_off;  // first word of the branch (8 * depth words)
+    uint32_t reserved[4]; // 160 bytes: a whole number of 8-byte units, and of 32-byte scalar loads
+};
+static_assert(sizeof(JobsVerifyDesc) == 160, "descriptor layout");
+
+// One 64-lane workgroup of jobs_verify_kernel: count (1..64) staged records from
+// `first` on, all of job `job`, or of no job (kJobsNone: job >= njobs).
+struct JobsVerifyBlock {
+    uint32_t job;
+    uint32_t first;
+    uint32_t count;
+    uint32_t reserved;
+};
+static_assert(sizeof(JobsVerifyBlock) == 16, "block table layout");
+static_assert(sizeof(bm_jobs_submit_t) == 32, "jobs submit layout");
+constexpr uint32_t kJobsNone = 0xFFFFFFFFu;
+constexpr uint32_t kJobsVerifyThreads = 64;
+
+namespace host {
+
+// What the three entries over several jobs refuse, ctx and set aside: every job is
+// checked, named by a submission or not.
+inline int jobs_verify_check(const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
+                             size_t nsessions, const bm_jobs_submit_t* submits, size_t n,
+                             const bm_job_verdict_t* verdicts, const void* out) {
+    if (!out || n > BM_MAX_JOB_SUBMITS || nsessions > BM_MAX_POOL_SESSIONS || njobs > BM_MAX_POOL_JOBS) return BM_EINVAL;
+    if ((n && (!submits || !verdicts)) || (nsessions && !sessions) || (njobs && !jobs)) return BM_EINVAL;
+    static const bm_pool_verify_result_t some = {};  // pool_verify_check only asks that there is one
+    for (size_t j = 0; j < njobs; ++j) {
+        // the arrays are checked above; a job is checked as for an empty batch
+        const int rc = pool_verify_check(&jobs[j].job, sessions, nsessions, nullptr, 0, nullptr, &some);
+        if (rc != BM_OK) return rc;
+    }
+    return BM_OK;
+}
+
+// The verdict of one submission over checked jobs (jobs_verify_check): the CPU path.
+inline void jobs_verify_one(const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
+                            size_t nsessions, const bm_jobs_submit_t& s, bm_job_verdict_t& v) {
+    if (s.job >= njobs) {
+        std::memset(&v, 0, sizeof v);
+        std::memset(v.hash, 0xFF, sizeof v.hash);
+        v.status = BM_SUBMIT_INVALID;
+        return;
+    }
+    const bm_pool_job_t& pj = jobs[s.job];
+    uint8_t bt[32];
+    const uint8_t* block_target = target_from_bits(pj.job.nbits, bt) ? bt : nullptr;
+    bm_pool_submit_t ps;
+    ps.extranonce2 = s.extranonce2;
+    ps.ntime = s.ntime;
+    ps.nonce = s.nonce;
+    ps.version = s.version;
+    ps.session = s.session;
+    pool_verify_one(&pj.job, sessions, nsessions, block_target, pj.ntime_lo, pj.ntime_hi, ps, v);
+}
+
+// The batch grouped by job: group g < njobs holds job g's submissions, group njobs
+// those of no job (job >= njobs), each in the caller's order.
+struct JobsPlan {
+    std::vector<uint32_t> start;            // njobs + 2 entries: group g is staged[start[g] .. start[g + 1])
+    std::vector<JobsVerifyBlock> blocks;    // sum over the groups of ceil(size / 64) entries
+};
+
+// The counts, by one read of every submission's job field: the groups' offsets and
+// the block table, which no entry of ever spans two groups.
+inline void jobs_plan(const bm_jobs_submit_t* submits, size_t n, size_t njobs, JobsPlan& P) {
+    P.start.assign(njobs + 2, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t g = submits[i].job < njobs ? submits[i].job : njobs;
+        ++P.start[g + 1];
+    }
+    for (size_t g = 0; g <= njobs; ++g) P.start[g + 1] += P.start[g];
+    P.blocks.clear();
+    for (size_t g = 0; g <= njobs; ++g)
+        for (uint32_t first = P.start[g]; first < P.start[g + 1]; first += kJobsVerifyThreads) {
+            const uint32_t left = P.start[g + 1] - first;
+            JobsVerifyBlock b;
+            b.job = g < njobs ? (uint32_t)g : kJobsNone;
+            b.first = first;
+            b.count = left < kJobsVerifyThreads ? left : kJobsVerifyThreads;
+            b.reserved = 0;
+            P.blocks.push_back(b);
+        }
+}
+
+// The stable scatter of the counting sort, which is the copy into the stage:
+// staged[k] is a submission with its original index in `job` (the job is the block
+// table's) and `reserved` zero.  staged has room for n records.
+inline void jobs_stage(const bm_jobs_submit_t* submits, size_t n, size_t njobs, const JobsPlan& P,
+                       bm_jobs_submit_t* staged) {
+    uint32_t cursor[BM_MAX_POOL_JOBS + 1];
+    for (size_t g = 0; g <= njobs; ++g) cursor[g] = P.start[g];
+    for (size_t i = 0; i < n; ++i) {
+        const size_t g = submits[i].job < njobs ? submits[i].job : njobs;
+        bm_jobs_submit_t& r = staged[cursor[g]++];
+        r = submits[i];
+        r.job = (uint32_t)i;
+        r.reserved = 0;
+    }
+}
+
+// What jobs_verify_kernel takes of checked jobs: a descriptor per job and the words
+// array, all tails and then all branches, big-endian.
+inline void jobs_verify_prepare(const bm_pool_job_t* jobs, size_t njobs, std::vector<JobsVerifyDesc>& desc,
+                                std::vector<uint32_t>& words) {
+    desc.assign(njobs, JobsVerifyDesc());
+    words.clear();
+    std::vector<std::vector<uint32_t>> branches(njobs);
+    std::vector<uint32_t> tail;
+    for (size_t j = 0; j < njobs; ++j) {
+        PoolVerifyArgs A;
+        pool_verify_prepare(&jobs[j].job, A, tail, branches[j]);
+        JobsVerifyDesc& D = desc[j];
+        std::memset(&D, 0, sizeof D);
+        std::memcpy(D.mid, A.mid, sizeof D.mid);
+        std::memcpy(D.prev, A.prev, sizeof D.prev);
+        std::memcpy(D.btgt, A.btgt, sizeof D.btgt);
+        D.nbits = A.nbits, D.has_block = A.has_block, D.nb = A.nb, D.j0 = A.j0, D.boff = A.boff;
+        D.size1 = A.size1, D.size2 = A.size2, D.depth = A.depth;
+        D.ntime_lo = jobs[j].ntime_lo, D.ntime_hi = jobs[j].ntime_hi;
+        D.tail_off = (uint32_t)words.size();
+        words.insert(words.end(), tail.begin(), tail.end());
+    }
+    for (size_t j = 0; j < njobs; ++j) {
+        desc[j].branch_off = (uint32_t)words.size();
+        words.insert(words.end(), branches[j].begin(), branches[j].end());
+    }
+}
+
+// The entries the device's answer is checked at by the CPU path: the ends of the
+// batch, every claimed block and the lowest-index submission of each job that has
+// one (the first staged record of its group: a descriptor or an offset taken from
+// another job shows there).  The status bits of `ignore` are not the verifier's.
+inline int jobs_verify_tripwire(const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
+                                size_t nsessions, const bm_jobs_submit_t* submits, size_t n, const JobsPlan& P,
+                                const bm_jobs_submit_t* staged, const bm_job_verdict_t* got, uint32_t ignore) {
+    auto same = [&](size_t i) {
+        bm_job_verdict_t want, have = got[i];
+        have.status &= ~ignore;
+        jobs_verify_one(jobs, njobs, sessions, nsessions, submits[i], want);
+        return std::memcmp(&want, &have, sizeof want) == 0;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        if (i != 0 && i != n - 1 && !(got[i].status & BM_SUBMIT_BLOCK)) continue;
+        if (!same(i)) return BM_EINTERNAL;
+    }
+    for (size_t g = 0; g < njobs; ++g) {
+        if (P.start[g] == P.start[g + 1]) continue;
+        const size_t i = staged[P.start[g]].job;
+        if (i >= n || !same(i)) return BM_EINTERNAL;
+    }
+    return BM_OK;
 }
 
 }  // namespace host

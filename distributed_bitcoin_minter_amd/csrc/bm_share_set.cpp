@@ -1,8 +1,9 @@
 // bm_share_set.cpp -- the entry points of the share set that need no GPU
 // (include/btcminer.h): bm_share_set_create_cpu, bm_share_set_destroy,
-// bm_share_set_clear, bm_share_set_count and bm_share_set_verify, which is the
-// specification on a CPU set and hands a device set to bm_aux.hip's operations
-// (bm_share_set_host.hpp).  Plain C++: no HIP in here.
+// bm_share_set_clear, bm_share_set_count, bm_share_set_verify and
+// bm_share_set_verify_jobs, which are the specification on a CPU set and hand a
+// device set to bm_aux.hip's operations (bm_share_set_host.hpp).  Plain C++: no HIP
+// in here.
 #include <new>
 #include <vector>
 
@@ -18,15 +19,12 @@ namespace bm {
 namespace {
 
 // The specification: one submission at a time, in the caller's order, over a hash
-// set of 32-byte arrays (host::share_set_apply).
-int verify_cpu(bm_share_set_t* set, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
-               const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
-               bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
-    uint8_t bt[32];
-    const uint8_t* block_target = host::target_from_bits(job->nbits, bt) ? bt : nullptr;
+// set of 32-byte arrays (host::share_set_apply).  one(i, v): the plain verdict of
+// submission i, bm_pool_verify_cpu's or bm_jobs_verify_cpu's.
+template <class One>
+int verify_cpu(bm_share_set_t* set, size_t n, One&& one, bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
     std::vector<bm_job_verdict_t> v(n);
-    for (size_t i = 0; i < n; ++i)
-        host::pool_verify_one(job, sessions, nsessions, block_target, ntime_lo, ntime_hi, submits[i], v[i]);
+    for (size_t i = 0; i < n; ++i) one(i, v[i]);
     uint64_t recorded = 0;
     BM_SHARE_TRY(host::share_set_apply(*set, v.data(), n, recorded));
     bm_share_set_result_t r;
@@ -96,7 +94,35 @@ int bm_share_set_verify(bm_share_set_t* set, const bm_job_t* job, const bm_pool_
     }
     if (set->ops) return set->ops->verify(set, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, verdicts, out);
     return bm::guarded([&] {
-        return bm::verify_cpu(set, job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, verdicts, out);
+        uint8_t bt[32];
+        const uint8_t* block_target = bm::host::target_from_bits(job->nbits, bt) ? bt : nullptr;
+        return bm::verify_cpu(
+            set, n,
+            [&](size_t i, bm_job_verdict_t& v) {
+                bm::host::pool_verify_one(job, sessions, nsessions, block_target, ntime_lo, ntime_hi, submits[i], v);
+            },
+            verdicts, out);
+    });
+}
+
+int bm_share_set_verify_jobs(bm_share_set_t* set, const bm_pool_job_t* jobs, size_t njobs,
+                             const bm_pool_session_t* sessions, size_t nsessions, const bm_jobs_submit_t* submits,
+                             size_t n, bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
+    const int rc = bm::host::share_set_jobs_check(set, jobs, njobs, sessions, nsessions, submits, n, verdicts, out);
+    if (rc != BM_OK) return rc;
+    if (n == 0) {  // legal, and changes nothing
+        std::memset(out, 0, sizeof *out);
+        out->count = set->count;
+        return BM_OK;
+    }
+    if (set->ops) return set->ops->verify_jobs(set, jobs, njobs, sessions, nsessions, submits, n, verdicts, out);
+    return bm::guarded([&] {
+        return bm::verify_cpu(
+            set, n,
+            [&](size_t i, bm_job_verdict_t& v) {
+                bm::host::jobs_verify_one(jobs, njobs, sessions, nsessions, submits[i], v);
+            },
+            verdicts, out);
     });
 }
 

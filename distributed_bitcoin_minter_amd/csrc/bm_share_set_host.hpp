@@ -38,6 +38,9 @@ struct ShareSetDeviceOps {
     int (*verify)(bm_share_set_t* set, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
                   const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
                   bm_job_verdict_t* verdicts, bm_share_set_result_t* out);
+    int (*verify_jobs)(bm_share_set_t* set, const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
+                       size_t nsessions, const bm_jobs_submit_t* submits, size_t n, bm_job_verdict_t* verdicts,
+                       bm_share_set_result_t* out);
     int (*clear)(bm_share_set_t* set);
     void (*destroy)(bm_share_set_t* set);  // the device's memory; the caller deletes the object
 };
@@ -51,6 +54,14 @@ inline int share_set_check(const bm_share_set_t* set, const bm_job_t* job, const
     if (!set || !out) return BM_EINVAL;
     static const bm_pool_verify_result_t some = {};  // pool_verify_check only asks that there is one
     return pool_verify_check(job, sessions, nsessions, submits, n, verdicts, &some);
+}
+
+// What bm_share_set_verify_jobs refuses, for either kind of set.
+inline int share_set_jobs_check(const bm_share_set_t* set, const bm_pool_job_t* jobs, size_t njobs,
+                                const bm_pool_session_t* sessions, size_t nsessions, const bm_jobs_submit_t* submits,
+                                size_t n, const bm_job_verdict_t* verdicts, const bm_share_set_result_t* out) {
+    if (!set || !out) return BM_EINVAL;
+    return jobs_verify_check(jobs, njobs, sessions, nsessions, submits, n, verdicts, out);
 }
 
 // *out of a call from its final verdicts, but for recorded and count.

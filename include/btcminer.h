@@ -705,10 +705,10 @@ int bm_pool_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const bm_pool_session
                        const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
                        bm_job_verdict_t* verdicts, bm_pool_verify_result_t* out);
 
-/* ---- duplicate-share detection: a per-job set of header hashes ------------------
+/* ---- duplicate-share detection: a set of header hashes ----------------------------
  * A pool that pays for shares must not pay twice for one.  A bm_share_set_t is an
- * opaque set of 32-byte header hashes with a fixed `capacity`; by convention it
- * holds one job (bm_share_set_clear starts the next).  bm_share_set_create makes
+ * opaque set of 32-byte header hashes with a fixed `capacity`; it is cleared by
+ * the caller when its jobs retire (bm_share_set_clear).  bm_share_set_create makes
  * it on the first device of ctx, where it lives across calls; bm_share_set_create_cpu
  * makes it in host memory, with no context: the specification.
  *
@@ -742,7 +742,7 @@ int bm_pool_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const bm_pool_session
  * Calls on one set are serialized by the caller, as calls on one context are (the
  * set uses its context's buffers and stream); two sets on one context are
  * independent.  bm_share_set_destroy(NULL) is fine; a device set is destroyed before
- * its context.  bm_share_set_clear forgets every hash (a new job);
+ * its context.  bm_share_set_clear forgets every hash (its jobs have retired);
  * bm_share_set_count reports the size and the capacity (either pointer may be NULL).
  *
  * The device set is an insert-only open-addressing table of 32-bit entry ids over a
@@ -767,8 +767,9 @@ int bm_pool_verify_gpu(bm_ctx_t* ctx, const bm_job_t* job, const bm_pool_session
  * arguments and the set's contents.  The host tripwire is bm_pool_verify_gpu's, with
  * BM_SUBMIT_DUPLICATE masked off.  bm_ctx_last_stats is left alone.
  *
- * Out of scope: vardiff policy; a network Stratum server; several jobs in one set or
- * one call; expiring or removing entries; sets over several devices or rank groups. */
+ * Out of scope: vardiff policy; a network Stratum server; expiring or removing
+ * entries; sets over several devices or rank groups.  Several jobs in one call:
+ * bm_share_set_verify_jobs, below. */
 #define BM_SUBMIT_DUPLICATE 16u       /* an eligible hash the set already held (bm_share_set_verify only) */
 #define BM_MAX_SHARE_SET (1u << 24)
 typedef struct bm_share_set bm_share_set_t;
@@ -787,6 +788,77 @@ int bm_share_set_count(const bm_share_set_t* set, uint64_t* count, uint64_t* cap
 int bm_share_set_verify(bm_share_set_t* set, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
                         const bm_pool_submit_t* submits, size_t n, uint32_t ntime_lo, uint32_t ntime_hi,
                         bm_job_verdict_t* verdicts, bm_share_set_result_t* out);
+
+/* ---- pool-side share verification over several live jobs in one call ------------
+ * A pool sends a new job every few tens of seconds and the earlier ones stay valid
+ * until the next block, so a batch read off the sockets mixes the submissions of
+ * several job ids.  bm_jobs_verify_* is bm_pool_verify_* with a table of jobs, each
+ * with its own ntime window, and a job index per submission; all jobs share the
+ * session table.
+ *   verdicts[i] is byte for byte what bm_pool_verify_cpu(&jobs[j].job, sessions,
+ *     nsessions, &that submission, 1, jobs[j].ntime_lo, jobs[j].ntime_hi, ...) gives,
+ *     j = submits[i].job: jobs[j].job is read as bm_pool_verify_* reads a job
+ *     (extranonce1 ignored, extranonce1_len 1..8 the size every session's
+ *     extranonce1 has under THIS job: its first extranonce1_len bytes count).
+ *   job >= njobs is BM_SUBMIT_INVALID exactly (hash all 0xFF, no other flag), as an
+ *     unknown session and an oversized extranonce2 are.
+ *   The order of `verdicts` is the caller's; `out` counts flags over the whole batch.
+ *   n == 0 succeeds and touches no array.  njobs == 0 with n > 0 is legal (`jobs`
+ *     may be NULL then): every entry is INVALID.
+ *   Jobs may differ in every field: the sizes of both extranonces, the coinbase's
+ *     length, the branch depth, nbits (decodable or not) and the window.
+ * BM_EINVAL: njobs > BM_MAX_POOL_JOBS; NULL `jobs` with njobs > 0; any job that
+ * bm_pool_verify_* refuses, whether or not a submission names it (all jobs are
+ * checked before anything is staged); everything bm_pool_verify_* refuses otherwise,
+ * a rank context with world > 1 among it.  On any failure `verdicts` and `out` are
+ * untouched and the context stays usable.
+ *
+ * bm_jobs_verify_cpu is pure CPU, no context: the specification.
+ * bm_jobs_verify_gpu gives byte-identical `verdicts` and `out`, on the first device
+ * of ctx.  The host groups the batch by job while it stages it (one stable counting
+ * sort, the scatter being the copy into the pinned buffer; the staged record carries
+ * the submission's original index where the caller's has `job`) and cuts every group
+ * into 64-lane workgroups, listed in a block table: no workgroup spans two jobs, so
+ * every loop of jobs_verify_kernel is wave-uniform and a workgroup's job descriptor,
+ * tail template and branch come through scalar loads.  One copy up (the job
+ * descriptors, all tails, all branches, the session table, the staged submissions,
+ * the block table), one launch, one copy back; verdicts are stored at the original
+ * index.  The host recomputes entries 0 and n - 1, every entry flagged BLOCK and the
+ * lowest-index submission of each job with the CPU path: BM_EINTERNAL on a difference.
+ *
+ * bm_share_set_verify_jobs is bm_share_set_verify over that verdict, on a CPU set or
+ * a device set: eligibility, lowest index wins, the all-or-nothing BM_EFULL and the
+ * poisoning are unchanged.  A set's key is the header hash, which already separates
+ * jobs (their coinbase, branch, prevhash or nbits differ): one set may hold several
+ * jobs' shares, is cleared by the caller when its jobs retire (bm_share_set_clear:
+ * a new block height), and may be fed by bm_share_set_verify and
+ * bm_share_set_verify_jobs alternately.  Two jobs[] entries with identical content
+ * give identical hashes: the same tuple under both is a duplicate.
+ *
+ * Out of scope: vardiff policy (a session whose difficulty changed between jobs is
+ * two session entries); a network Stratum server; splitting a batch over devices;
+ * rank groups; expiring single jobs from a set. */
+#define BM_MAX_POOL_JOBS 64
+typedef struct bm_pool_job {
+    bm_job_t job;                     /* as bm_pool_verify_* reads it: extranonce1 ignored, extranonce1_len 1..8 */
+    uint32_t ntime_lo, ntime_hi;      /* this job's window, inclusive */
+} bm_pool_job_t;
+typedef struct bm_jobs_submit {
+    uint64_t extranonce2;
+    uint32_t ntime, nonce, version, session; /* as bm_pool_submit_t */
+    uint32_t job;                     /* index into jobs[] */
+    uint32_t reserved;                /* ignored */
+} bm_jobs_submit_t;                   /* 32 bytes */
+
+int bm_jobs_verify_cpu(const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions, size_t nsessions,
+                       const bm_jobs_submit_t* submits, size_t n, bm_job_verdict_t* verdicts,
+                       bm_pool_verify_result_t* out);
+int bm_jobs_verify_gpu(bm_ctx_t* ctx, const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
+                       size_t nsessions, const bm_jobs_submit_t* submits, size_t n, bm_job_verdict_t* verdicts,
+                       bm_pool_verify_result_t* out);
+int bm_share_set_verify_jobs(bm_share_set_t* set, const bm_pool_job_t* jobs, size_t njobs,
+                             const bm_pool_session_t* sessions, size_t nsessions, const bm_jobs_submit_t* submits,
+                             size_t n, bm_job_verdict_t* verdicts, bm_share_set_result_t* out);
 
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */

@@ -130,6 +130,40 @@ inline bm_pool_verify_result_t verify_pool_submits_cpu(const Job& job, const std
     return r;
 }
 
+// One live job of a pool and its own ntime window, inclusive (bm_pool_job_t)
+struct PoolJob {
+    const Job* job = nullptr;  // borrowed: lives, unchanged, through the call
+    uint32_t ntime_lo = 0, ntime_hi = 0xFFFFFFFFu;
+};
+
+// The C view of a job table: valid while the jobs live and their buffers do not change
+inline std::vector<bm_pool_job_t> pool_job_views(const std::vector<PoolJob>& jobs, const char* what) {
+    std::vector<bm_pool_job_t> v(jobs.size());
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        if (!jobs[i].job || jobs[i].job->branch.size() % 32 != 0) throw Error(BM_EINVAL, what);
+        v[i].job = jobs[i].job->view();
+        v[i].ntime_lo = jobs[i].ntime_lo;
+        v[i].ntime_hi = jobs[i].ntime_hi;
+    }
+    return v;
+}
+
+// Context::verify_jobs without a GPU or a context: bm_jobs_verify_cpu, the
+// specification of the GPU entry
+inline bm_pool_verify_result_t verify_jobs_cpu(const std::vector<PoolJob>& jobs,
+                                               const std::vector<bm_pool_session_t>& sessions,
+                                               const bm_jobs_submit_t* submits, size_t n,
+                                               std::vector<bm_job_verdict_t>& verdicts) {
+    const std::vector<bm_pool_job_t> j = pool_job_views(jobs, "verify_jobs_cpu");
+    bm_pool_verify_result_t r;
+    std::vector<bm_job_verdict_t> buf(n);
+    check(bm_jobs_verify_cpu(j.empty() ? nullptr : j.data(), j.size(), sessions.empty() ? nullptr : sessions.data(),
+                             sessions.size(), submits, n, n ? buf.data() : nullptr, &r),
+          "bm_jobs_verify_cpu");
+    verdicts = std::move(buf);
+    return r;
+}
+
 // Owns a bm_ctx.  Not thread-safe, like the C context (one per OS thread).
 class Context {
    public:
@@ -321,6 +355,22 @@ class Context {
         verdicts = std::move(buf);
         return r;
     }
+    // the submissions of several live jobs (submits[i].job picks the job and its
+    // window; all jobs share the session table) in one call, verdicts in the
+    // caller's order, on the first device: bm_jobs_verify_gpu
+    bm_pool_verify_result_t verify_jobs(const std::vector<PoolJob>& jobs, const std::vector<bm_pool_session_t>& sessions,
+                                        const bm_jobs_submit_t* submits, size_t n,
+                                        std::vector<bm_job_verdict_t>& verdicts) {
+        const std::vector<bm_pool_job_t> j = pool_job_views(jobs, "verify_jobs");
+        bm_pool_verify_result_t r;
+        std::vector<bm_job_verdict_t> buf(n);
+        check(bm_jobs_verify_gpu(ctx_, j.empty() ? nullptr : j.data(), j.size(),
+                                 sessions.empty() ? nullptr : sessions.data(), sessions.size(), submits, n,
+                                 n ? buf.data() : nullptr, &r),
+              "bm_jobs_verify_gpu");
+        verdicts = std::move(buf);
+        return r;
+    }
     // the double SHA-256 of the header under each nonce, 32 bytes each, most
     // significant byte first, on the first device: bm_header_hash_gpu
     std::vector<uint8_t> header_hash(const uint8_t header[80], const std::vector<uint32_t>& nonces) {
@@ -359,8 +409,8 @@ class Context {
     bm_ctx_t* ctx_ = nullptr;
 };
 
-// A bm_share_set_t: the set of header hashes behind duplicate-share detection, by
-// convention one job's.  ShareSet(ctx, capacity) lives on the first device of ctx,
+// A bm_share_set_t: the set of header hashes behind duplicate-share detection,
+// cleared by the caller when its jobs retire.  ShareSet(ctx, capacity) lives on the first device of ctx,
 // across calls, and is destroyed before ctx; ShareSet::cpu(capacity) lives in host
 // memory and needs no GPU: the specification.  Move-only.
 class ShareSet {
@@ -401,7 +451,21 @@ class ShareSet {
         verdicts = std::move(buf);
         return r;
     }
-    void clear() { check(bm_share_set_clear(set_), "bm_share_set_clear"); }  // a new job
+    // Context::verify_jobs plus the set, as verify: bm_share_set_verify_jobs
+    bm_share_set_result_t verify_jobs(const std::vector<PoolJob>& jobs, const std::vector<bm_pool_session_t>& sessions,
+                                      const bm_jobs_submit_t* submits, size_t n,
+                                      std::vector<bm_job_verdict_t>& verdicts) {
+        const std::vector<bm_pool_job_t> j = pool_job_views(jobs, "ShareSet::verify_jobs");
+        bm_share_set_result_t r;
+        std::vector<bm_job_verdict_t> buf(n);
+        check(bm_share_set_verify_jobs(set_, j.empty() ? nullptr : j.data(), j.size(),
+                                       sessions.empty() ? nullptr : sessions.data(), sessions.size(), submits, n,
+                                       n ? buf.data() : nullptr, &r),
+              "bm_share_set_verify_jobs");
+        verdicts = std::move(buf);
+        return r;
+    }
+    void clear() { check(bm_share_set_clear(set_), "bm_share_set_clear"); }  // the set's jobs have retired
     uint64_t count() const {
         uint64_t n = 0;
         check(bm_share_set_count(set_, &n, nullptr), "bm_share_set_count");
