@@ -17,6 +17,7 @@ from ._lib import (BM_EFULL, BM_MAX_SHARE_SET, BM_SUBMIT_DUPLICATE, BtcMinerErro
                    parse_pool_submit, parse_submit, plan_segments, rccl_unique_id, roll_versions, submit_params,
                    verify_pool_submits_cpu, verify_submits_cpu)
 from ._lib import BM_MAX_POOL_JOBS, JobsSubmit, PoolJob, parse_jobs_submit, verify_jobs_submits_cpu
+from ._lib import BM_MAX_LEDGER_ROWS, Ledger, LedgerResult, LedgerRow
 from .miner import Miner
 
 __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", "HeaderHitsResult",
@@ -26,4 +27,4 @@ __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", 
            "verify_submits_cpu", "PoolSession", "PoolSubmit", "PoolVerifyResult", "parse_pool_submit",
            "verify_pool_submits_cpu", "ShareSet", "ShareSetResult", "BM_SUBMIT_DUPLICATE", "BM_EFULL",
            "BM_MAX_SHARE_SET", "PoolJob", "JobsSubmit", "parse_jobs_submit", "verify_jobs_submits_cpu",
-           "BM_MAX_POOL_JOBS"]
+           "BM_MAX_POOL_JOBS", "Ledger", "LedgerRow", "LedgerResult", "BM_MAX_LEDGER_ROWS"]

@@ -256,6 +256,34 @@ class JobsSubmit(ctypes.Structure):
                 ("job", c_u32), ("reserved", c_u32)]
 
 
+BM_MAX_LEDGER_ROWS = 1 << 20
+BM_LEDGER_NO_BEST = (1 << 64) - 1
+
+
+class LedgerRow(ctypes.Structure):
+    """bm_ledger_row_t: one account's tallies.  An empty row is seven zeros and
+    best = 2^64 - 1."""
+    _fields_ = [("accepted", c_u64), ("blocks", c_u64), ("above_target", c_u64), ("ntime", c_u64),
+                ("duplicates", c_u64), ("invalid", c_u64), ("work", c_u64), ("best", c_u64)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+    @property
+    def rejected(self) -> int:
+        """Every submission of the row that was not credited."""
+        return self.above_target + self.ntime + self.duplicates + self.invalid
+
+
+class LedgerResult(ctypes.Structure):
+    """bm_ledger_result_t: ShareSetResult's counts (the last three 0 without a
+    set), then the call's credited submissions, those of unknown sessions and the
+    credited work."""
+    _fields_ = [("n", c_u64), ("shares", c_u64), ("blocks", c_u64), ("invalid", c_u64), ("ntime", c_u64),
+                ("duplicates", c_u64), ("recorded", c_u64), ("count", c_u64),
+                ("credited", c_u64), ("unattributed", c_u64), ("work", c_u64)]
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -367,6 +395,17 @@ def _open(path):
         "bm_share_set_count": ([vp, P(c_u64), P(c_u64)], ctypes.c_int),
         "bm_share_set_verify": ([vp, P(JobStruct), P(PoolSessionStruct), ctypes.c_size_t, P(PoolSubmit), ctypes.c_size_t,
                                  c_u32, c_u32, P(JobVerdict), P(ShareSetResult)], ctypes.c_int),
+        "bm_ledger_create": ([vp, ctypes.c_size_t, P(vp)], ctypes.c_int),
+        "bm_ledger_create_cpu": ([ctypes.c_size_t, P(vp)], ctypes.c_int),
+        "bm_ledger_destroy": ([vp], None),
+        "bm_ledger_clear": ([vp], ctypes.c_int),
+        "bm_ledger_rows": ([vp, P(c_u64)], ctypes.c_int),
+        "bm_ledger_read": ([vp, ctypes.c_size_t, ctypes.c_size_t, P(LedgerRow)], ctypes.c_int),
+        "bm_ledger_drain": ([vp, ctypes.c_size_t, ctypes.c_size_t, P(LedgerRow)], ctypes.c_int),
+        "bm_ledger_set_peel": ([vp, c_u32], ctypes.c_int),
+        "bm_ledger_verify_jobs": ([vp, vp, P(PoolJobStruct), ctypes.c_size_t, P(PoolSessionStruct), ctypes.c_size_t,
+                                   P(c_u32), P(c_u64), P(JobsSubmit), ctypes.c_size_t, P(JobVerdict),
+                                   P(LedgerResult)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -939,6 +978,118 @@ class ShareSet:
         under two jobs[] entries of identical content is a duplicate."""
         return _jobs_verify(lambda *a: self._lib.bm_share_set_verify_jobs(self.handle, *a), "bm_share_set_verify_jobs",
                             jobs, sessions, submits, ShareSetResult)
+
+
+class Ledger:
+    """A bm_ledger_t: the per-account tallies behind share accounting -- `rows`
+    LedgerRow counters fed by verify_jobs and read or drained at payout or
+    retarget time.  Ledger(ctx, rows) lives on the first device of ctx, across
+    calls, and is closed before ctx; Ledger.cpu(rows) lives in host memory and
+    needs no GPU: the specification.  Not thread-safe, and a device ledger shares
+    its context's buffers: one call at a time per context."""
+
+    def __init__(self, ctx, rows: int, lib_path=None):
+        self._h = None
+        if not isinstance(rows, int) or isinstance(rows, bool) or not 1 <= rows <= BM_MAX_LEDGER_ROWS:
+            raise ValueError(f"rows must be in 1..{BM_MAX_LEDGER_ROWS}, got {rows!r}")
+        h = ctypes.c_void_p()
+        if ctx is None:
+            self._lib = load(lib_path)
+            check(self._lib.bm_ledger_create_cpu(rows, ctypes.byref(h)), "bm_ledger_create_cpu")
+        else:
+            self._lib = ctx._lib
+            check(self._lib.bm_ledger_create(ctx.handle, rows, ctypes.byref(h)), "bm_ledger_create")
+        self._ctx = ctx  # a device ledger must not outlive its context
+        self._h = h
+
+    @classmethod
+    def cpu(cls, rows: int, lib_path=None):
+        """A ledger in host memory (bm_ledger_create_cpu)."""
+        return cls(None, rows, lib_path)
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("ledger closed")
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            if self._ctx is None or self._ctx._h is not None:  # (a closed context took the device's memory with it)
+                self._lib.bm_ledger_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def rows(self) -> int:
+        rows = c_u64(0)
+        check(self._lib.bm_ledger_rows(self.handle, ctypes.byref(rows)), "bm_ledger_rows")
+        return rows.value
+
+    def clear(self):
+        """Empty every row."""
+        check(self._lib.bm_ledger_clear(self.handle), "bm_ledger_clear")
+
+    def set_peel(self, rounds: int):
+        """The device kernel's combine rounds, 0..64 (a CPU ledger ignores them)."""
+        check(self._lib.bm_ledger_set_peel(self.handle, _u32(rounds, "rounds")), "bm_ledger_set_peel")
+
+    def _range(self, call, what, first, count):
+        if count is None:
+            count = max(self.rows - first, 0)
+        for v, name in ((first, "first"), (count, "count")):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+        out = (LedgerRow * count)()
+        check(call(self.handle, first, count, out if count else None), what)
+        return out
+
+    def read(self, first: int = 0, count=None):
+        """Rows [first, first + count) as a (LedgerRow * count) array; count None:
+        to the end."""
+        return self._range(self._lib.bm_ledger_read, "bm_ledger_read", first, count)
+
+    def drain(self, first: int = 0, count=None):
+        """read, then exactly those rows are empty again."""
+        return self._range(self._lib.bm_ledger_drain, "bm_ledger_drain", first, count)
+
+    def verify_jobs(self, jobs, sessions, submits, share_set=None, accounts=None, weights=None):
+        """ShareSet.verify_jobs (or, without share_set, Context.verify_jobs_submits)
+        plus the credit of every submission to the row of its session's account
+        (bm_ledger_verify_jobs) -> (verdicts, LedgerResult).  accounts: one row
+        index per session (None: session s -> row s); weights: one u64 per session
+        (None: 1 each).  All or nothing, as ShareSet.verify_jobs."""
+        if not isinstance(sessions, ctypes.Array):
+            sessions = list(sessions)
+        nses = len(sessions)
+        acc = wgt = None
+        if accounts is not None:
+            accounts = [_u32(a, "account") for a in accounts]
+            if len(accounts) != nses:
+                raise ValueError(f"accounts has one entry per session ({nses}), got {len(accounts)}")
+            acc = (c_u32 * max(nses, 1))(*accounts)
+        if weights is not None:
+            weights = list(weights)
+            if len(weights) != nses:
+                raise ValueError(f"weights has one entry per session ({nses}), got {len(weights)}")
+            for w in weights:
+                if not isinstance(w, int) or isinstance(w, bool) or not 0 <= w <= U64_MAX:
+                    raise ValueError(f"a weight must be in 0..2^64-1, got {w!r}")
+            wgt = (c_u64 * max(nses, 1))(*weights)
+        sh = share_set.handle if share_set is not None else None
+        return _jobs_verify(lambda *a: self._lib.bm_ledger_verify_jobs(self.handle, sh, *a[:4], acc, wgt, *a[4:]),
+                            "bm_ledger_verify_jobs", jobs, sessions, submits, LedgerResult)
 
 
 def _header_bytes(header) -> bytes:

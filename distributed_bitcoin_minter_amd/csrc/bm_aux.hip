@@ -2,10 +2,10 @@
 // kernels of bm_aux_kernels.hpp, the host wrapper the searches launch the
 // second-pass reduction through, and the entry points outside the search
 // path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu, and bm_job_verify_gpu,
-// bm_pool_verify_gpu, bm_jobs_verify_gpu and the device side of bm_share_set_verify
-// and bm_share_set_verify_jobs, whose kernels have units of their own,
-// bm_job_verify_inst.hip, bm_pool_verify_inst.hip, bm_jobs_verify_inst.hip and
-// bm_share_set_inst.hip).  See
+// bm_pool_verify_gpu, bm_jobs_verify_gpu and the device side of bm_share_set_verify,
+// bm_share_set_verify_jobs and bm_ledger_verify_jobs, whose kernels have units of
+// their own, bm_job_verify_inst.hip, bm_pool_verify_inst.hip, bm_jobs_verify_inst.hip,
+// bm_share_set_inst.hip and bm_ledger_inst.hip).  See
 // bm_runtime.hpp for the layout of the host runtime.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 
 #include "bm_aux_kernels.hpp"
 #include "bm_job.hpp"
+#include "bm_ledger_host.hpp"
 #include "bm_runtime.hpp"
 #include "bm_share_set_host.hpp"
 
@@ -201,6 +202,19 @@ struct PoolStage {
     uint32_t* d_out = nullptr;        // the verdicts on the device
     uint64_t* d_lanes = nullptr;      // lane_u units after them
     const bm_job_verdict_t* got = nullptr;  // the verdicts' place in the pinned copy
+    // jobs_verify_launch only: the staged records on the device, and where a ledger's extras start (below)
+    const bm_jobs_submit_t* d_sub = nullptr;
+    size_t extra_at = 0;
+};
+
+// What a ledger adds to jobs_verify_launch's copy up, between the block table and
+// ctl: accounts[] (32-bit, padded to a unit), weights[] and the credit kernel's
+// control words, zero.  NULL accounts are staged as the identity, NULL weights as ones.
+struct LedgerStage {
+    const uint32_t* accounts;
+    const uint64_t* weights;
+    static size_t acc_units(size_t ses_staged) { return (ses_staged + 1) / 2; }
+    static size_t units(size_t ses_staged) { return acc_units(ses_staged) + ses_staged + kLedgerCtlUnits; }
 };
 
 int pool_verify_launch(DeviceCtx& d, const bm_job_t* job, const bm_pool_session_t* sessions, size_t nsessions,
@@ -291,14 +305,15 @@ const void* g_jobs_verify = nullptr;
 // What bm_jobs_verify_gpu and bm_share_set_verify_jobs share: the grouping, the stage
 // and the launch of jobs_verify_kernel.  The buffers are job_verify_impl's.  Device
 // buffer, in 8-byte units:
-//   descriptors | words (all tails, all branches) | sessions | staged submits | block table | ctl | verdicts | lanes
-// with ctl and lanes as in pool_verify_launch, and the verdicts and what follows them
+//   descriptors | words (all tails, all branches) | sessions | staged submits | block table | extras | ctl | verdicts | lanes
+// with ctl and lanes as in pool_verify_launch, extras a ledger's (LedgerStage; none without one), and the verdicts and what follows them
 // where PoolStage says, so the share set's kernels take them unchanged.  The counting
 // sort's scatter is the copy of the submissions into the pinned buffer; plan and
 // *staged (the pinned copy of the staged records) stay valid for the tripwire.
 int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, const bm_pool_session_t* sessions,
                        size_t nsessions, const bm_jobs_submit_t* submits, size_t n, size_t ctl_u, size_t lane_u,
-                       PoolStage& st, host::JobsPlan& plan, const bm_jobs_submit_t** staged) {
+                       PoolStage& st, host::JobsPlan& plan, const bm_jobs_submit_t** staged,
+                       const LedgerStage* lg = nullptr) {
     if (!g_jobs_verify) return BM_EINTERNAL;
     std::vector<JobsVerifyDesc> desc;
     std::vector<uint32_t> words;
@@ -310,7 +325,8 @@ int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, co
     const size_t desc_u = desc_staged * sizeof(JobsVerifyDesc) / 8, words_u = words.size() / 2;
     const size_t ses_u = ses_staged * sizeof(bm_pool_session_t) / 8, sub_u = n * sizeof(bm_jobs_submit_t) / 8;
     const size_t blk_u = plan.blocks.size() * sizeof(JobsVerifyBlock) / 8;
-    const size_t in_u = desc_u + words_u + ses_u + sub_u + blk_u + ctl_u;
+    const size_t extra_u = lg ? LedgerStage::units(ses_staged) : 0;
+    const size_t in_u = desc_u + words_u + ses_u + sub_u + blk_u + extra_u + ctl_u;
     const size_t out_u = n * sizeof(bm_job_verdict_t) / 8;
     BM_TRY(grow(d, d.h_verify, d.hverify_cap, in_u + out_u, sizeof(uint64_t), true));
     BM_TRY(grow(d, d.d_verify, d.verify_cap, in_u + out_u + lane_u));
@@ -338,6 +354,15 @@ int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, co
     const size_t blk_at = at;
     std::memcpy(stage + at, plan.blocks.data(), 8 * blk_u);
     at += blk_u;
+    const size_t extra_at = at;
+    if (lg) {
+        std::memset(stage + at, 0, 8 * extra_u);
+        uint32_t* acc = reinterpret_cast<uint32_t*>(stage + at);
+        uint64_t* wgt = stage + at + LedgerStage::acc_units(ses_staged);
+        for (size_t s = 0; s < nsessions; ++s) acc[s] = lg->accounts ? lg->accounts[s] : (uint32_t)s;
+        for (size_t s = 0; s < nsessions; ++s) wgt[s] = lg->weights ? lg->weights[s] : 1ull;
+        at += extra_u;
+    }
     if (ctl_u) std::memset(stage + at, 0, 8 * ctl_u);
     BM_HIP(hipMemcpyAsync(d.d_verify, stage, 8 * in_u, hipMemcpyHostToDevice, d.stream));
     const JobsVerifyDesc* d_desc = reinterpret_cast<const JobsVerifyDesc*>(d.d_verify + desc_at);
@@ -355,6 +380,8 @@ int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, co
     st.d_out = d_out;
     st.d_lanes = d.d_verify + in_u + out_u;
     st.got = reinterpret_cast<const bm_job_verdict_t*>(d.h_verify + in_u);
+    st.d_sub = d_sub;
+    st.extra_at = extra_at;
     *staged = h_staged;
     return BM_OK;
 }
@@ -405,9 +432,11 @@ int share_set_rollback(DeviceCtx& d, const ShareSetArgs& S, uint32_t* d_slots, c
 // the batch does not fit.  `tripwire` is that verifier's, over the verdicts with
 // BM_SUBMIT_DUPLICATE masked off.  The caller's arrays are written last.  From the insert's
 // launch to the end of the commit or rollback the table holds this call's candidate
-// ids: a failure in between poisons the set until it is cleared.
-template <class Launch, class Tripwire>
-int share_set_verify_impl(bm_share_set_t* set, size_t n, Launch&& launch, Tripwire&& tripwire,
+// ids: a failure in between poisons the set until it is cleared.  `after` (the
+// ledger's credit; nothing for the plain calls) runs once the commit is enqueued, over
+// the stage and the final verdicts; its failure is one of those.
+template <class Launch, class Tripwire, class After>
+int share_set_verify_impl(bm_share_set_t* set, size_t n, Launch&& launch, Tripwire&& tripwire, After&& after,
                           bm_job_verdict_t* verdicts, bm_share_set_result_t* out) {
     if (!g_share_insert || !g_share_resolve || !g_share_commit || !g_share_rollback) return BM_EINTERNAL;
     if (set->poisoned) return BM_EINTERNAL;
@@ -465,6 +494,7 @@ int share_set_verify_impl(bm_share_set_t* set, size_t n, Launch&& launch, Tripwi
         void* args[] = {&S, &d_verdicts, &keys, &d_slots, &lane_slot, &lane_rank};
         BM_HIP(hipLaunchKernel(g_share_commit, grid, block, args, 0, d.stream));
     }
+    BM_TRY(after(d, st));
     BM_HIP(hipStreamSynchronize(d.stream));
     set->poisoned = false;
     set->count += winners;
@@ -499,7 +529,7 @@ int share_set_verify_op(bm_share_set_t* set, const bm_job_t* job, const bm_pool_
                 return pool_verify_tripwire(job, sessions, nsessions, submits, n, ntime_lo, ntime_hi, got,
                                             BM_SUBMIT_DUPLICATE);
             },
-            verdicts, out);
+            [](DeviceCtx&, const PoolStage&) { return (int)BM_OK; }, verdicts, out);
     });
 }
 
@@ -519,7 +549,7 @@ int share_set_verify_jobs_op(bm_share_set_t* set, const bm_pool_job_t* jobs, siz
                 return host::jobs_verify_tripwire(jobs, njobs, sessions, nsessions, submits, n, plan, staged, got,
                                                   BM_SUBMIT_DUPLICATE);
             },
-            verdicts, out);
+            [](DeviceCtx&, const PoolStage&) { return (int)BM_OK; }, verdicts, out);
     });
 }
 
@@ -558,6 +588,173 @@ int share_set_create_impl(bm_ctx* ctx, bm_share_set_t* set) {
         return e == hipErrorOutOfMemory ? BM_ENOMEM : BM_EHIP;
     }
     return share_set_clear_impl(set);
+}
+
+// ---- the ledger on a device (bm_ledger_host.hpp, bm_ledger.hpp) ----
+// The two kernels, registered by bm_ledger_inst.hip at load time
+const void* g_ledger_credit = nullptr;
+const void* g_ledger_fill = nullptr;
+
+// The empty-row pattern over rows [first, first + count), enqueued.
+int ledger_fill(DeviceCtx& d, bm_ledger_t* ledger, size_t first, size_t count) {
+    if (!g_ledger_fill) return BM_EINTERNAL;
+    if (count == 0) return BM_OK;
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(ledger->d_rows) + kLedgerRowWords * first;
+    uint64_t nwords = (uint64_t)kLedgerRowWords * count;
+    const uint32_t grid = (uint32_t)((nwords + kLedgerFillThreads - 1) / kLedgerFillThreads);
+    void* args[] = {&words, &nwords};
+    BM_HIP(hipLaunchKernel(g_ledger_fill, dim3(grid), dim3(kLedgerFillThreads), args, 0, d.stream));
+    return BM_OK;
+}
+
+// The credit of a verified batch, once the call can no longer be refused: the launch
+// of ledger_credit_kernel over the stage of jobs_verify_launch (with a LedgerStage)
+// and the final verdicts on the device, its seven control words back, and their
+// compare with the totals of the verdicts the host holds (`want`).  From the launch
+// on the rows may hold a part of this call: a failure poisons the ledger.
+int ledger_credit(bm_ledger_t* ledger, DeviceCtx& d, const PoolStage& st, size_t n, size_t nsessions,
+                  const host::LedgerTotals& want) {
+    const size_t ses_staged = nsessions ? nsessions : 1;
+    LedgerArgs A;
+    A.n = (uint32_t)n;
+    A.nsessions = (uint32_t)nsessions;
+    A.rows = (uint32_t)ledger->rows;
+    A.rounds = ledger->peel;
+    const uint32_t* d_sub = reinterpret_cast<const uint32_t*>(st.d_sub);
+    const uint32_t* d_verdicts = st.d_out;
+    const uint32_t* d_acc = reinterpret_cast<const uint32_t*>(d.d_verify + st.extra_at);
+    const uint64_t* d_wgt = d.d_verify + st.extra_at + LedgerStage::acc_units(ses_staged);
+    const size_t ctl_at = st.extra_at + LedgerStage::acc_units(ses_staged) + ses_staged;
+    uint64_t* d_ctl = d.d_verify + ctl_at;
+    uint64_t* d_rows = ledger->d_rows;
+    void* args[] = {&A, &d_sub, &d_verdicts, &d_acc, &d_wgt, &d_rows, &d_ctl};
+    ledger->poisoned = true;
+    BM_HIP(hipLaunchKernel(g_ledger_credit, dim3((uint32_t)((n + kLedgerThreads - 1) / kLedgerThreads)),
+                           dim3(kLedgerThreads), args, 0, d.stream));
+    BM_HIP(hipMemcpyAsync(d.h_verify + ctl_at, d_ctl, 8 * kLedgerCtlWords, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    if (std::memcmp(d.h_verify + ctl_at, want.word, 8 * kLedgerCtlWords) != 0) return BM_EINTERNAL;
+    ledger->poisoned = false;
+    return BM_OK;
+}
+
+// bm_ledger_verify_jobs on a device ledger: share_set_verify_impl with the credit as
+// its step after the commit, or without a set jobs_verify_impl's shape with the credit
+// after the tripwire.  The caller's arrays are written last.
+int ledger_verify_jobs_impl(bm_ledger_t* ledger, bm_share_set_t* set, const bm_pool_job_t* jobs, size_t njobs,
+                            const bm_pool_session_t* sessions, size_t nsessions, const uint32_t* accounts,
+                            const uint64_t* weights, const bm_jobs_submit_t* submits, size_t n,
+                            bm_job_verdict_t* verdicts, bm_ledger_result_t* out) {
+    if (!g_ledger_credit || !g_jobs_verify) return BM_EINTERNAL;
+    if (ledger->poisoned) return BM_EINTERNAL;
+    const LedgerStage lg = {accounts, weights};
+    host::JobsPlan plan;
+    const bm_jobs_submit_t* staged = nullptr;
+    host::LedgerTotals t;
+    bm_share_set_result_t r;
+    if (set) {
+        BM_TRY(share_set_verify_impl(
+            set, n,
+            [&](DeviceCtx& d, PoolStage& st) {
+                return jobs_verify_launch(d, jobs, njobs, sessions, nsessions, submits, n, 1, n, st, plan, &staged, &lg);
+            },
+            [&](const bm_job_verdict_t* got) {
+                return host::jobs_verify_tripwire(jobs, njobs, sessions, nsessions, submits, n, plan, staged, got,
+                                                  BM_SUBMIT_DUPLICATE);
+            },
+            [&](DeviceCtx& d, const PoolStage& st) {
+                host::ledger_totals(submits, st.got, n, nsessions, weights, t);
+                return ledger_credit(ledger, d, st, n, nsessions, t);
+            },
+            verdicts, &r));
+    } else {
+        DeviceCtx& d = ledger->ctx->devs[0];
+        BM_HIP(hipSetDevice(d.id));
+        PoolStage st;
+        BM_TRY(jobs_verify_launch(d, jobs, njobs, sessions, nsessions, submits, n, 0, 0, st, plan, &staged, &lg));
+        BM_HIP(hipMemcpyAsync(d.h_verify + st.in_u, st.d_out, 8 * st.out_u, hipMemcpyDeviceToHost, d.stream));
+        BM_HIP(hipStreamSynchronize(d.stream));
+        BM_TRY(host::jobs_verify_tripwire(jobs, njobs, sessions, nsessions, submits, n, plan, staged, st.got, 0));
+        host::ledger_totals(submits, st.got, n, nsessions, weights, t);
+        BM_TRY(ledger_credit(ledger, d, st, n, nsessions, t));
+        host::share_set_count(st.got, n, r);
+        std::memcpy(verdicts, st.got, n * sizeof(bm_job_verdict_t));
+    }
+    host::ledger_result(r, t, *out);
+    return BM_OK;
+}
+
+int ledger_verify_jobs_op(bm_ledger_t* ledger, bm_share_set_t* set, const bm_pool_job_t* jobs, size_t njobs,
+                          const bm_pool_session_t* sessions, size_t nsessions, const uint32_t* accounts,
+                          const uint64_t* weights, const bm_jobs_submit_t* submits, size_t n,
+                          bm_job_verdict_t* verdicts, bm_ledger_result_t* out) {
+    DeviceGuard guard;
+    return guarded([&] {
+        return ledger_verify_jobs_impl(ledger, set, jobs, njobs, sessions, nsessions, accounts, weights, submits, n,
+                                       verdicts, out);
+    });
+}
+
+// bm_ledger_read and bm_ledger_drain: one copy down on the stream and, for a drain,
+// the fill of exactly those rows behind it.  The caller's array is written last.
+int ledger_read_impl(bm_ledger_t* ledger, size_t first, size_t count, bool drain, bm_ledger_row_t* out) {
+    if (ledger->poisoned) return BM_EINTERNAL;
+    if (count == 0) return BM_OK;
+    DeviceCtx& d = ledger->ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    std::vector<bm_ledger_row_t> tmp(count);
+    BM_HIP(hipMemcpyAsync(tmp.data(), ledger->d_rows + kLedgerRowWords * first, count * sizeof(bm_ledger_row_t),
+                          hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    if (drain) {
+        ledger->poisoned = true;
+        BM_TRY(ledger_fill(d, ledger, first, count));
+        BM_HIP(hipStreamSynchronize(d.stream));
+        ledger->poisoned = false;
+    }
+    std::memcpy(out, tmp.data(), count * sizeof(bm_ledger_row_t));
+    return BM_OK;
+}
+
+int ledger_read_op(bm_ledger_t* ledger, size_t first, size_t count, bool drain, bm_ledger_row_t* out) {
+    DeviceGuard guard;
+    return guarded([&] { return ledger_read_impl(ledger, first, count, drain, out); });
+}
+
+int ledger_clear_op(bm_ledger_t* ledger) {
+    DeviceGuard guard;
+    DeviceCtx& d = ledger->ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    BM_TRY(ledger_fill(d, ledger, 0, ledger->rows));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    ledger->poisoned = false;
+    return BM_OK;
+}
+
+void ledger_destroy_op(bm_ledger_t* ledger) {
+    DeviceGuard guard;
+    DeviceCtx& d = ledger->ctx->devs[0];
+    (void)hipSetDevice(d.id);
+    (void)hipStreamSynchronize(d.stream);
+    if (ledger->d_rows) (void)hipFree(ledger->d_rows);
+    ledger->d_rows = nullptr;
+}
+
+const LedgerDeviceOps kLedgerOps = {ledger_verify_jobs_op, ledger_read_op, ledger_clear_op, ledger_destroy_op};
+
+// The ledger's device array, every row empty.  A failed allocation leaves the context
+// as it was.
+int ledger_create_impl(bm_ctx* ctx, bm_ledger_t* ledger) {
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, sizeof(bm_ledger_row_t) * ledger->rows);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? BM_ENOMEM : BM_EHIP;
+    }
+    ledger->d_rows = static_cast<uint64_t*>(p);
+    return ledger_clear_op(ledger);
 }
 
 }  // namespace
@@ -626,6 +823,28 @@ int bm_share_set_create(bm_ctx_t* ctx, size_t capacity, bm_share_set_t** out) {
         return rc;
     }
     *out = set;
+    return BM_OK;
+}
+
+void bm_register_ledger_kernels(const void* credit, const void* fill) {
+    bm::g_ledger_credit = credit;
+    bm::g_ledger_fill = fill;
+}
+
+int bm_ledger_create(bm_ctx_t* ctx, size_t rows, bm_ledger_t** out) {
+    if (!ctx || !out || rows == 0 || rows > BM_MAX_LEDGER_ROWS) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    bm_ledger_t* ledger = new (std::nothrow) bm_ledger;
+    if (!ledger) return BM_ENOMEM;
+    ledger->rows = rows;
+    ledger->ctx = ctx;
+    ledger->ops = &bm::kLedgerOps;
+    const int rc = bm::ledger_create_impl(ctx, ledger);
+    if (rc != BM_OK) {
+        bm_ledger_destroy(ledger);
+        return rc;
+    }
+    *out = ledger;
     return BM_OK;
 }
 

@@ -860,6 +860,109 @@ int bm_share_set_verify_jobs(bm_share_set_t* set, const bm_pool_job_t* jobs, siz
                              const bm_pool_session_t* sessions, size_t nsessions, const bm_jobs_submit_t* submits,
                              size_t n, bm_job_verdict_t* verdicts, bm_share_set_result_t* out);
 
+/* ---- share accounting: a per-account ledger ------------------------------------------
+ * A pool verifies shares to pay for them: each accepted share is credited to an
+ * account, weighted by the difficulty it was mined at, and the per-account reject
+ * counts feed vardiff and ban rules.  A bm_ledger_t is an opaque table of `rows`
+ * bm_ledger_row_t counters.  bm_ledger_create makes it on the first device of ctx,
+ * where it lives across calls as a share set does; bm_ledger_create_cpu makes it in
+ * host memory, with no context: the specification.  It holds tallies, not policy:
+ * no vardiff rule and no payout scheme.
+ *
+ * bm_ledger_verify_jobs verifies a batch, de-duplicates it and credits it in one call.
+ *   With a set, `verdicts` and the first eight fields of `out` are byte for byte
+ *     bm_share_set_verify_jobs's for the same arguments and the same set, and the set
+ *     changes as it does there.  With set == NULL they are bm_jobs_verify_cpu's, the
+ *     three set fields (duplicates, recorded, count) zero.
+ *   accounts[s] is the row of session s and weights[s] its weight (its difficulty in
+ *     the caller's fixed-point unit).  accounts == NULL: session s -> row s.
+ *     weights == NULL: 1 each.  Several sessions may share a row, with different
+ *     weights.
+ *   Every submission with session < nsessions falls into exactly one CLASS, by its
+ *     final status; the first rule that applies decides:
+ *       1. BM_SUBMIT_INVALID               -> invalid  (an unknown job among them)
+ *       2. BM_SUBMIT_NTIME                 -> ntime
+ *       3. BM_SUBMIT_DUPLICATE             -> duplicates
+ *       4. BM_SUBMIT_SHARE or _BLOCK       -> accepted, and also blocks with _BLOCK
+ *       5. otherwise                       -> above_target
+ *     and the class word of row accounts[session] grows by one.  An accepted
+ *     submission also adds weights[session] to the row's `work` (wrapping) and lowers
+ *     its `best` to hash[0..7] read as a big-endian integer.  out->credited and
+ *     out->work count the same credit over the whole call.
+ *   A submission with session >= nsessions touches no row and counts in
+ *     out->unattributed.  out->n = the call's row class deltas + unattributed.
+ *   Every sum is an integer add or a min: the rows depend on the multiset of
+ *     submissions, never on their order, and a device ledger holds the same bytes as
+ *     a CPU ledger.  `work` is a sum over submissions, not weight x count per row.
+ *   All or nothing: on any failure (BM_EINVAL, the set's BM_EFULL, a tripwire's
+ *     BM_EINTERNAL, a failed allocation) `verdicts`, `out`, the ledger and the set are
+ *     as before.  The exception is the share set's: a failure after the ledger
+ *     kernel's launch (a HIP error, or control words that do not match) poisons the
+ *     ledger until bm_ledger_clear -- every call on it but clear and destroy returns
+ *     BM_EINTERNAL -- and, with a set, the set too, whose commit has been enqueued.
+ *   n == 0 is legal and changes nothing (*out: zeros and the set's count).
+ * bm_ledger_read copies rows [first, first + count) out; bm_ledger_drain does the
+ * same and then resets exactly those rows to empty (seven zeros and best =
+ * UINT64_MAX); bm_ledger_clear empties every row; bm_ledger_rows reports the size.
+ * bm_ledger_set_peel sets the device kernel's combine rounds (below; 0..64, default
+ * 64: a wave combines until no lane is pending); a CPU ledger accepts and ignores it.
+ * BM_EINVAL: everything bm_share_set_verify_jobs or bm_jobs_verify_* refuses; a NULL
+ * ledger; `rows` of 0 or above BM_MAX_LEDGER_ROWS; any accounts[s] >= rows (every
+ * session is checked before anything is staged); accounts == NULL with nsessions >
+ * rows; a device ledger with a CPU set, a CPU ledger with a device set, a set on
+ * another context; first + count > rows; rounds > 64; a rank context with world > 1.
+ * Calls on one ledger are serialized by the caller, as calls on one context are; two
+ * ledgers on one context are independent.  bm_ledger_destroy(NULL) is fine; a device
+ * ledger is destroyed before its context.
+ *
+ * The device call is bm_share_set_verify_jobs's (or bm_jobs_verify_gpu's) with
+ * accounts[] and weights[] in the same single copy up, and ledger_credit_kernel
+ * launched once the call can no longer be refused: after share_commit_kernel is
+ * enqueued, or without a set after the tripwire.  One lane per staged record reads its
+ * session, its final status and the first two hash words.  Before any global atomic a
+ * wave combines, for up to `rounds` rounds: the row of its first pending lane, a ballot
+ * of the lanes on that row, popcounts for the class counts, a wave sum for `work`, a
+ * wave min for `best`, then that row's non-zero updates once (64-bit no-return
+ * atomicAdd / atomicMin).  Lanes still pending issue their own atomics; rounds = 0 is
+ * the per-lane form.  Nothing spins or waits on another lane.  The kernel also sums the
+ * call's class totals and work into seven control words, which the host compares with
+ * the totals of the verdicts: BM_EINTERNAL and a poisoned ledger on a difference.
+ *
+ * Out of scope: vardiff and payout policy; a network Stratum server; ledgers over
+ * several devices or rank groups; single-job entries (njobs = 1 serves them). */
+#define BM_MAX_LEDGER_ROWS (1u << 20)
+typedef struct bm_ledger bm_ledger_t;
+typedef struct bm_ledger_row {          /* 64 bytes; an empty row is seven zeros and best = UINT64_MAX */
+    uint64_t accepted;      /* credited submissions */
+    uint64_t blocks;        /* credited submissions with BM_SUBMIT_BLOCK */
+    uint64_t above_target;  /* hashed, neither SHARE nor BLOCK */
+    uint64_t ntime;         /* outside their job's window */
+    uint64_t duplicates;    /* BM_SUBMIT_DUPLICATE */
+    uint64_t invalid;       /* BM_SUBMIT_INVALID with a known session */
+    uint64_t work;          /* sum of the session's weight over credited submissions, modulo 2^64 */
+    uint64_t best;          /* min over credited submissions of hash[0..7] read as a big-endian u64 */
+} bm_ledger_row_t;
+typedef struct bm_ledger_result {       /* 88 bytes */
+    uint64_t n, shares, blocks, invalid, ntime, duplicates, recorded, count; /* bm_share_set_result_t's; the last three 0 without a set */
+    uint64_t credited;      /* submissions of class accepted */
+    uint64_t unattributed;  /* session >= nsessions: no row was touched */
+    uint64_t work;          /* this call's credited work, modulo 2^64 */
+} bm_ledger_result_t;
+
+int bm_ledger_create(bm_ctx_t* ctx, size_t rows, bm_ledger_t** out);
+int bm_ledger_create_cpu(size_t rows, bm_ledger_t** out);
+void bm_ledger_destroy(bm_ledger_t* ledger);
+int bm_ledger_clear(bm_ledger_t* ledger);
+int bm_ledger_rows(const bm_ledger_t* ledger, uint64_t* rows);
+int bm_ledger_read(bm_ledger_t* ledger, size_t first, size_t count, bm_ledger_row_t* out);
+int bm_ledger_drain(bm_ledger_t* ledger, size_t first, size_t count, bm_ledger_row_t* out);
+int bm_ledger_set_peel(bm_ledger_t* ledger, uint32_t rounds);
+int bm_ledger_verify_jobs(bm_ledger_t* ledger, bm_share_set_t* set /* or NULL */, const bm_pool_job_t* jobs,
+                          size_t njobs, const bm_pool_session_t* sessions, size_t nsessions,
+                          const uint32_t* accounts /* nsessions entries, or NULL */,
+                          const uint64_t* weights /* nsessions entries, or NULL */, const bm_jobs_submit_t* submits,
+                          size_t n, bm_job_verdict_t* verdicts, bm_ledger_result_t* out);
+
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */
 int bm_hash_gpu(bm_ctx_t* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,

@@ -483,6 +483,75 @@ class ShareSet {
     bm_share_set_t* set_ = nullptr;
 };
 
+// Owns a bm_ledger_t: the per-account tallies behind share accounting, fed by
+// verify_jobs and read or drained at payout or retarget time.  On the first device
+// of a context (destroy it before the context), or Ledger::cpu(rows) in host memory
+// with no GPU: the specification.  Not thread-safe; a device ledger shares its
+// context's buffers, so one call at a time per context.
+class Ledger {
+   public:
+    Ledger(Context& ctx, size_t rows) { check(bm_ledger_create(ctx.get(), rows, &ledger_), "bm_ledger_create"); }
+    static Ledger cpu(size_t rows) {
+        Ledger l;
+        check(bm_ledger_create_cpu(rows, &l.ledger_), "bm_ledger_create_cpu");
+        return l;
+    }
+    Ledger(const Ledger&) = delete;
+    Ledger& operator=(const Ledger&) = delete;
+    Ledger(Ledger&& o) noexcept : ledger_(o.ledger_) { o.ledger_ = nullptr; }
+    Ledger& operator=(Ledger&& o) noexcept {
+        if (this != &o) {
+            bm_ledger_destroy(ledger_);
+            ledger_ = o.ledger_;
+            o.ledger_ = nullptr;
+        }
+        return *this;
+    }
+    ~Ledger() { bm_ledger_destroy(ledger_); }
+
+    // ShareSet::verify_jobs (set == nullptr: Context::verify_jobs) plus the credit of
+    // every submission to the row of its session's account: bm_ledger_verify_jobs.
+    // accounts and weights have one entry per session, or are nullptr (session s ->
+    // row s; 1 each).  All or nothing, as ShareSet::verify_jobs.
+    bm_ledger_result_t verify_jobs(ShareSet* set, const std::vector<PoolJob>& jobs,
+                                   const std::vector<bm_pool_session_t>& sessions, const uint32_t* accounts,
+                                   const uint64_t* weights, const bm_jobs_submit_t* submits, size_t n,
+                                   std::vector<bm_job_verdict_t>& verdicts) {
+        const std::vector<bm_pool_job_t> j = pool_job_views(jobs, "Ledger::verify_jobs");
+        bm_ledger_result_t r;
+        std::vector<bm_job_verdict_t> buf(n);
+        check(bm_ledger_verify_jobs(ledger_, set ? set->get() : nullptr, j.empty() ? nullptr : j.data(), j.size(),
+                                    sessions.empty() ? nullptr : sessions.data(), sessions.size(), accounts, weights,
+                                    submits, n, n ? buf.data() : nullptr, &r),
+              "bm_ledger_verify_jobs");
+        verdicts = std::move(buf);
+        return r;
+    }
+    std::vector<bm_ledger_row_t> read(size_t first, size_t count) {
+        std::vector<bm_ledger_row_t> out(count);
+        check(bm_ledger_read(ledger_, first, count, count ? out.data() : nullptr), "bm_ledger_read");
+        return out;
+    }
+    // read, then exactly those rows are empty again
+    std::vector<bm_ledger_row_t> drain(size_t first, size_t count) {
+        std::vector<bm_ledger_row_t> out(count);
+        check(bm_ledger_drain(ledger_, first, count, count ? out.data() : nullptr), "bm_ledger_drain");
+        return out;
+    }
+    void clear() { check(bm_ledger_clear(ledger_), "bm_ledger_clear"); }
+    void set_peel(uint32_t rounds) { check(bm_ledger_set_peel(ledger_, rounds), "bm_ledger_set_peel"); }  // 0..64
+    uint64_t rows() const {
+        uint64_t n = 0;
+        check(bm_ledger_rows(ledger_, &n), "bm_ledger_rows");
+        return n;
+    }
+    bm_ledger_t* get() const { return ledger_; }
+
+   private:
+    Ledger() = default;
+    bm_ledger_t* ledger_ = nullptr;
+};
+
 }  // namespace btcminer
 
 namespace bitcoin {

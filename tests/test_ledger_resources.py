@@ -1,0 +1,23 @@
+"""The built ledger kernels' resources (no GPU): the unit's resource remarks."""
+import os
+
+import pytest
+
+from conftest import ROOT
+
+BUILD = os.path.join(ROOT, "distributed_bitcoin_minter_amd", "csrc", "build")
+KERNELS = ("ledger_credit_kernel", "ledger_fill_kernel")
+
+
+def test_kernel_resources():
+    """No scratch, no spills and no LDS, in either kernel."""
+    path = os.path.join(BUILD, "bm_ledger_inst.res")
+    if not os.path.exists(path):
+        pytest.skip("device assembly not built (make -C distributed_bitcoin_minter_amd/csrc)")
+    with open(path) as f:
+        res = f.read()
+    for kernel in KERNELS:
+        assert kernel in res, kernel
+    assert res.count("Function Name:") == len(KERNELS)
+    for line in ("ScratchSize [bytes/lane]: 0", "SGPRs Spill: 0", "VGPRs Spill: 0", "LDS Size [bytes/block]: 0"):
+        assert res.count(line) == len(KERNELS), (line, res[-1500:])
