@@ -18,6 +18,8 @@ from ._lib import (BM_EFULL, BM_MAX_SHARE_SET, BM_SUBMIT_DUPLICATE, BtcMinerErro
                    verify_pool_submits_cpu, verify_submits_cpu)
 from ._lib import BM_MAX_POOL_JOBS, JobsSubmit, PoolJob, parse_jobs_submit, verify_jobs_submits_cpu
 from ._lib import BM_MAX_LEDGER_ROWS, Ledger, LedgerResult, LedgerRow
+from ._lib import (SessionState, SessionTable, VardiffChange, VardiffPolicy, VardiffResult,
+                   difficulty_fx_to_target)
 from .miner import Miner
 
 __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", "HeaderHitsResult",
@@ -27,4 +29,5 @@ __all__ = ["bitcoin", "dist", "Miner", "Context", "BtcMinerError", "HeaderHit", 
            "verify_submits_cpu", "PoolSession", "PoolSubmit", "PoolVerifyResult", "parse_pool_submit",
            "verify_pool_submits_cpu", "ShareSet", "ShareSetResult", "BM_SUBMIT_DUPLICATE", "BM_EFULL",
            "BM_MAX_SHARE_SET", "PoolJob", "JobsSubmit", "parse_jobs_submit", "verify_jobs_submits_cpu",
-           "BM_MAX_POOL_JOBS", "Ledger", "LedgerRow", "LedgerResult", "BM_MAX_LEDGER_ROWS"]
+           "BM_MAX_POOL_JOBS", "Ledger", "LedgerRow", "LedgerResult", "BM_MAX_LEDGER_ROWS",
+           "SessionTable", "SessionState", "VardiffPolicy", "VardiffChange", "VardiffResult", "difficulty_fx_to_target"]

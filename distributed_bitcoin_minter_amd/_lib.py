@@ -284,6 +284,45 @@ class LedgerResult(ctypes.Structure):
                 ("credited", c_u64), ("unattributed", c_u64), ("work", c_u64)]
 
 
+class SessionInit(ctypes.Structure):
+    """bm_session_init_t: what bm_sessions_set takes per slot; difficulty_fx in
+    units of 2^-32, 0 closes the slot."""
+    _fields_ = [("extranonce1", ctypes.c_uint8 * 8), ("difficulty_fx", c_u64), ("account", c_u32), ("reserved", c_u32)]
+
+
+class SessionState(ctypes.Structure):
+    """bm_session_state_t: a slot's difficulty, the start of its window, the
+    accepted submissions since then and its changes since it was set."""
+    _fields_ = [("difficulty_fx", c_u64), ("since_ms", c_u64), ("accepted", c_u64), ("retargets", c_u64)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
+class VardiffPolicyStruct(ctypes.Structure):
+    """bm_vardiff_policy_t."""
+    _fields_ = [("target_ms", c_u64), ("window_ms", c_u64), ("min_difficulty_fx", c_u64), ("max_difficulty_fx", c_u64),
+                ("burst", c_u32), ("band_permille", c_u32), ("max_up", c_u32), ("max_down", c_u32)]
+
+
+class VardiffChange(ctypes.Structure):
+    """bm_vardiff_change_t: one changed slot of a retarget; target is T(new_fx)."""
+    _fields_ = [("session", c_u32), ("reserved", c_u32), ("old_fx", c_u64), ("new_fx", c_u64),
+                ("target", ctypes.c_uint8 * 32)]
+
+    def as_tuple(self):
+        return (self.session, self.old_fx, self.new_fx, int.from_bytes(bytes(self.target), "big"))
+
+
+class VardiffResult(ctypes.Structure):
+    """bm_vardiff_result_t: the open, evaluated and changed slots of a retarget,
+    and the changed ones that went up and down."""
+    _fields_ = [("open", c_u64), ("evaluated", c_u64), ("changed", c_u64), ("raised", c_u64), ("lowered", c_u64)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
 class Segment(ctypes.Structure):
     _fields_ = [("p", c_i32), ("nbv", c_i32), ("pad_block", c_i32), ("digits", c_i32), ("nd", c_i32),
                 ("max_inner", c_i32), ("vlo", c_u64), ("vhi", c_u64), ("nonce_base", c_u64),
@@ -406,6 +445,19 @@ def _open(path):
         "bm_ledger_verify_jobs": ([vp, vp, P(PoolJobStruct), ctypes.c_size_t, P(PoolSessionStruct), ctypes.c_size_t,
                                    P(c_u32), P(c_u64), P(JobsSubmit), ctypes.c_size_t, P(JobVerdict),
                                    P(LedgerResult)], ctypes.c_int),
+        "bm_target_from_difficulty_fx": ([c_u64, P(ctypes.c_uint8)], ctypes.c_int),
+        "bm_sessions_create": ([vp, ctypes.c_size_t, P(vp)], ctypes.c_int),
+        "bm_sessions_create_cpu": ([ctypes.c_size_t, P(vp)], ctypes.c_int),
+        "bm_sessions_destroy": ([vp], None),
+        "bm_sessions_clear": ([vp], ctypes.c_int),
+        "bm_sessions_count": ([vp, P(c_u64), P(c_u64)], ctypes.c_int),
+        "bm_sessions_set": ([vp, P(c_u32), ctypes.c_size_t, P(SessionInit), c_u64], ctypes.c_int),
+        "bm_sessions_get": ([vp, ctypes.c_size_t, ctypes.c_size_t, P(PoolSessionStruct), P(c_u32), P(c_u64),
+                             P(SessionState)], ctypes.c_int),
+        "bm_sessions_verify_jobs": ([vp, vp, vp, P(PoolJobStruct), ctypes.c_size_t, P(JobsSubmit), ctypes.c_size_t,
+                                     P(JobVerdict), P(LedgerResult)], ctypes.c_int),
+        "bm_sessions_retarget": ([vp, c_u64, P(VardiffPolicyStruct), P(VardiffChange), ctypes.c_size_t,
+                                  P(VardiffResult)], ctypes.c_int),
         "bm_hash_gpu": ([vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u64), ctypes.c_size_t, P(c_u64)],
                         ctypes.c_int),
         "bm_ctx_set_timing": ([vp, ctypes.c_int], ctypes.c_int),
@@ -534,6 +586,17 @@ def difficulty_to_target(difficulty) -> int:
     buf = (ctypes.c_uint8 * 32)()
     if load().bm_target_from_difficulty(d, buf) != BM_OK:
         raise ValueError(f"difficulty must be a finite number above 0, got {difficulty!r}")
+    return int.from_bytes(bytes(buf), "big")
+
+
+def difficulty_fx_to_target(difficulty_fx: int) -> int:
+    """A difficulty in units of 2^-32 as a target: floor(0xffff * 2^240 /
+    difficulty_fx), exact and never saturating (bm_target_from_difficulty_fx, pure
+    CPU); ValueError outside 1..2^64-1."""
+    if not isinstance(difficulty_fx, int) or isinstance(difficulty_fx, bool) or not 1 <= difficulty_fx <= U64_MAX:
+        raise ValueError(f"difficulty_fx must be in 1..2^64-1, got {difficulty_fx!r}")
+    buf = (ctypes.c_uint8 * 32)()
+    check(load().bm_target_from_difficulty_fx(difficulty_fx, buf), "bm_target_from_difficulty_fx")
     return int.from_bytes(bytes(buf), "big")
 
 
@@ -1090,6 +1153,191 @@ class Ledger:
         sh = share_set.handle if share_set is not None else None
         return _jobs_verify(lambda *a: self._lib.bm_ledger_verify_jobs(self.handle, sh, *a[:4], acc, wgt, *a[4:]),
                             "bm_ledger_verify_jobs", jobs, sessions, submits, LedgerResult)
+
+
+class VardiffPolicy:
+    """bm_vardiff_policy_t: a share should take target_ms; a session is evaluated
+    once its window is window_ms long or, with burst != 0, once it has `burst`
+    accepted shares; one step multiplies the difficulty by at most max_up and
+    divides it by at most max_down, inside [min_difficulty_fx, max_difficulty_fx],
+    and a change within band_permille / 1000 of the old difficulty is none."""
+    FIELDS = ("target_ms", "window_ms", "min_difficulty_fx", "max_difficulty_fx", "burst", "band_permille", "max_up",
+              "max_down")
+
+    def __init__(self, target_ms=10_000, window_ms=60_000, min_difficulty_fx=1, max_difficulty_fx=U64_MAX, burst=0,
+                 band_permille=250, max_up=4, max_down=4):
+        self.target_ms, self.window_ms = target_ms, window_ms
+        self.min_difficulty_fx, self.max_difficulty_fx = min_difficulty_fx, max_difficulty_fx
+        self.burst, self.band_permille, self.max_up, self.max_down = burst, band_permille, max_up, max_down
+
+    @property
+    def struct(self):
+        s = VardiffPolicyStruct()
+        for f, (_, t) in zip(self.FIELDS, VardiffPolicyStruct._fields_):
+            v = getattr(self, f)
+            top = U64_MAX if t is c_u64 else U32_MAX
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= top:
+                raise ValueError(f"{f} must be in 0..{top}, got {v!r}")
+            setattr(s, f, v)
+        return s
+
+    def __repr__(self):
+        return "VardiffPolicy(%s)" % ", ".join(f"{f}={getattr(self, f)}" for f in self.FIELDS)
+
+
+class SessionTable:
+    """A bm_sessions_t: the pool's sessions -- extranonce1, share target, account
+    and weight per slot -- and a SessionState per slot, kept across calls so that a
+    verify call copies no session, with the vardiff step on top.
+    SessionTable(ctx, capacity) lives on the first device of ctx and is closed
+    before ctx; SessionTable.cpu(capacity) lives in host memory and needs no GPU:
+    the specification.  Not thread-safe, and a device table shares its context's
+    buffers: one call at a time per context."""
+
+    def __init__(self, ctx, capacity: int, lib_path=None):
+        self._h = None
+        if not isinstance(capacity, int) or isinstance(capacity, bool) or not 1 <= capacity <= BM_MAX_POOL_SESSIONS:
+            raise ValueError(f"capacity must be in 1..{BM_MAX_POOL_SESSIONS}, got {capacity!r}")
+        h = ctypes.c_void_p()
+        if ctx is None:
+            self._lib = load(lib_path)
+            check(self._lib.bm_sessions_create_cpu(capacity, ctypes.byref(h)), "bm_sessions_create_cpu")
+        else:
+            self._lib = ctx._lib
+            check(self._lib.bm_sessions_create(ctx.handle, capacity, ctypes.byref(h)), "bm_sessions_create")
+        self._ctx = ctx  # a device table must not outlive its context
+        self._h = h
+
+    @classmethod
+    def cpu(cls, capacity: int, lib_path=None):
+        """A table in host memory (bm_sessions_create_cpu)."""
+        return cls(None, capacity, lib_path)
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("session table closed")
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            if self._ctx is None or self._ctx._h is not None:  # (a closed context took the device's memory with it)
+                self._lib.bm_sessions_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _sizes(self):
+        count, capacity = c_u64(0), c_u64(0)
+        check(self._lib.bm_sessions_count(self.handle, ctypes.byref(count), ctypes.byref(capacity)), "bm_sessions_count")
+        return count.value, capacity.value
+
+    @property
+    def count(self) -> int:
+        """1 + the highest slot set since the last clear."""
+        return self._sizes()[0]
+
+    @property
+    def capacity(self) -> int:
+        return self._sizes()[1]
+
+    def clear(self):
+        """count = 0 and every slot never set."""
+        check(self._lib.bm_sessions_clear(self.handle), "bm_sessions_clear")
+
+    def set(self, entries, now_ms: int, index=None):
+        """Slot index[j] (index None: slot j) becomes entries[j], an
+        (extranonce1, difficulty_fx, account) triple -- difficulty_fx 0 closes the
+        slot -- with a fresh state whose window starts at now_ms
+        (bm_sessions_set).  A slot named twice takes its later entry."""
+        rows = [tuple(e) for e in entries]
+        arr = (SessionInit * max(len(rows), 1))()
+        for a, row in zip(arr, rows):
+            if len(row) != 3:
+                raise ValueError(f"an entry is (extranonce1, difficulty_fx, account), got {row!r}")
+            en1, fx, account = row
+            if not isinstance(en1, (bytes, bytearray)) or len(en1) > 8:
+                raise ValueError(f"extranonce1 must be at most 8 bytes, got {en1!r}")
+            if not isinstance(fx, int) or isinstance(fx, bool) or not 0 <= fx <= U64_MAX:
+                raise ValueError(f"difficulty_fx must be in 0..2^64-1, got {fx!r}")
+            ctypes.memmove(a.extranonce1, bytes(en1), len(en1))
+            a.difficulty_fx, a.account = fx, _u32(account, "account")
+        idx = None
+        if index is not None:
+            index = [_u32(i, "index") for i in index]
+            if len(index) != len(rows):
+                raise ValueError(f"index has one entry per session ({len(rows)}), got {len(index)}")
+            idx = (c_u32 * max(len(rows), 1))(*index)
+        if not isinstance(now_ms, int) or isinstance(now_ms, bool) or not 0 <= now_ms <= U64_MAX:
+            raise ValueError(f"now_ms must be in 0..2^64-1, got {now_ms!r}")
+        check(self._lib.bm_sessions_set(self.handle, idx, len(rows), arr, now_ms), "bm_sessions_set")
+
+    def _range(self, first, count):
+        if count is None:
+            count = max(self.count - first, 0)
+        for v, name in ((first, "first"), (count, "count")):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+        return first, count
+
+    def get(self, first: int = 0, count=None):
+        """Slots [first, first + count) as the arrays the pool calls take ->
+        ((PoolSessionStruct * count), accounts, weights); count None: up to the
+        table's count (bm_sessions_get)."""
+        first, count = self._range(first, count)
+        ses, acc, wgt = (PoolSessionStruct * count)(), (c_u32 * count)(), (c_u64 * count)()
+        check(self._lib.bm_sessions_get(self.handle, first, count, ses, acc, wgt, None), "bm_sessions_get")
+        return ses, list(acc), list(wgt)
+
+    def state(self, first: int = 0, count=None):
+        """The states of slots [first, first + count) as a (SessionState * count) array."""
+        first, count = self._range(first, count)
+        out = (SessionState * count)()
+        check(self._lib.bm_sessions_get(self.handle, first, count, None, None, None, out), "bm_sessions_get")
+        return out
+
+    def verify_jobs(self, jobs, submits, ledger=None, share_set=None):
+        """Ledger.verify_jobs over the table's sessions, accounts and weights
+        (bm_sessions_verify_jobs) -> (verdicts, LedgerResult); every accepted
+        submission also counts in its slot's state.  ledger None: no row changes."""
+        jarr, _rows = _jobs_array(jobs)
+        arr = _jobs_submit_array(submits)
+        if len(arr) > BM_MAX_JOB_SUBMITS:
+            raise ValueError(f"at most {BM_MAX_JOB_SUBMITS} submissions per call, got {len(arr)}")
+        verdicts = (JobVerdict * len(arr))()
+        r = LedgerResult()
+        check(self._lib.bm_sessions_verify_jobs(self.handle, ledger.handle if ledger is not None else None,
+                                                share_set.handle if share_set is not None else None,
+                                                jarr if len(jarr) else None, len(jarr), arr if len(arr) else None,
+                                                len(arr), verdicts if len(arr) else None, ctypes.byref(r)),
+              "bm_sessions_verify_jobs")
+        return verdicts, r
+
+    def retarget(self, now_ms: int, policy, cap=None):
+        """One vardiff step at now_ms (bm_sessions_retarget) -> (changes, a list of
+        VardiffChange ascending by session, VardiffResult); cap None: room for
+        every slot.  BtcMinerError with status BM_EFULL when more than cap slots
+        change: the table is as before."""
+        if cap is None:
+            cap = self.count
+        if not isinstance(cap, int) or isinstance(cap, bool) or cap < 0:
+            raise ValueError(f"cap must be a non-negative integer, got {cap!r}")
+        p = policy.struct
+        changes = (VardiffChange * max(cap, 1))()
+        r = VardiffResult()
+        check(self._lib.bm_sessions_retarget(self.handle, now_ms, ctypes.byref(p), changes if cap else None, cap,
+                                             ctypes.byref(r)), "bm_sessions_retarget")
+        return list(changes[: r.changed]), r
 
 
 def _header_bytes(header) -> bytes:

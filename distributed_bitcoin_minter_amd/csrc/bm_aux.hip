@@ -3,12 +3,14 @@
 // second-pass reduction through, and the entry points outside the search
 // path (bm_reduce_gpu, bm_hash_gpu, bm_header_hash_gpu, and bm_job_verify_gpu,
 // bm_pool_verify_gpu, bm_jobs_verify_gpu and the device side of bm_share_set_verify,
-// bm_share_set_verify_jobs and bm_ledger_verify_jobs, whose kernels have units of
-// their own, bm_job_verify_inst.hip, bm_pool_verify_inst.hip, bm_jobs_verify_inst.hip,
-// bm_share_set_inst.hip and bm_ledger_inst.hip).  See
+// bm_share_set_verify_jobs, bm_ledger_verify_jobs and the session table, whose kernels
+// have units of their own, bm_job_verify_inst.hip, bm_pool_verify_inst.hip,
+// bm_jobs_verify_inst.hip, bm_share_set_inst.hip, bm_ledger_inst.hip and
+// bm_sessions_inst.hip).  See
 // bm_runtime.hpp for the layout of the host runtime.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -16,6 +18,7 @@
 #include "bm_job.hpp"
 #include "bm_ledger_host.hpp"
 #include "bm_runtime.hpp"
+#include "bm_sessions_host.hpp"
 #include "bm_share_set_host.hpp"
 
 namespace bm {
@@ -205,14 +208,24 @@ struct PoolStage {
     // jobs_verify_launch only: the staged records on the device, and where a ledger's extras start (below)
     const bm_jobs_submit_t* d_sub = nullptr;
     size_t extra_at = 0;
+    // with a LedgerStage: accounts[] and weights[] on the device, and where the credit's control words are
+    const uint32_t* d_acc = nullptr;
+    const uint64_t* d_wgt = nullptr;
+    size_t ctl_at = 0;
 };
 
 // What a ledger adds to jobs_verify_launch's copy up, between the block table and
 // ctl: accounts[] (32-bit, padded to a unit), weights[] and the credit kernel's
 // control words, zero.  NULL accounts are staged as the identity, NULL weights as ones.
+// A session table (bm_sessions_t) has the three per-session arrays on the device
+// already: with d_sessions set they are neither staged nor copied, the kernels get
+// these pointers, and the extras are the control words alone.
 struct LedgerStage {
     const uint32_t* accounts;
     const uint64_t* weights;
+    const uint32_t* d_sessions = nullptr;
+    const uint32_t* d_accounts = nullptr;
+    const uint64_t* d_weights = nullptr;
     static size_t acc_units(size_t ses_staged) { return (ses_staged + 1) / 2; }
     static size_t units(size_t ses_staged) { return acc_units(ses_staged) + ses_staged + kLedgerCtlUnits; }
 };
@@ -323,9 +336,10 @@ int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, co
     // every array on the device has an entry; no lane reads either
     const size_t ses_staged = nsessions ? nsessions : 1, desc_staged = njobs ? njobs : 1;
     const size_t desc_u = desc_staged * sizeof(JobsVerifyDesc) / 8, words_u = words.size() / 2;
-    const size_t ses_u = ses_staged * sizeof(bm_pool_session_t) / 8, sub_u = n * sizeof(bm_jobs_submit_t) / 8;
+    const bool resident = lg && lg->d_sessions;  // a session table's arrays: nothing per session is staged
+    const size_t ses_u = resident ? 0 : ses_staged * sizeof(bm_pool_session_t) / 8, sub_u = n * sizeof(bm_jobs_submit_t) / 8;
     const size_t blk_u = plan.blocks.size() * sizeof(JobsVerifyBlock) / 8;
-    const size_t extra_u = lg ? LedgerStage::units(ses_staged) : 0;
+    const size_t extra_u = !lg ? 0 : resident ? (size_t)kLedgerCtlUnits : LedgerStage::units(ses_staged);
     const size_t in_u = desc_u + words_u + ses_u + sub_u + blk_u + extra_u + ctl_u;
     const size_t out_u = n * sizeof(bm_job_verdict_t) / 8;
     BM_TRY(grow(d, d.h_verify, d.hverify_cap, in_u + out_u, sizeof(uint64_t), true));
@@ -342,7 +356,7 @@ int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, co
     if (words_u) std::memcpy(stage + at, words.data(), 8 * words_u);
     at += words_u;
     const size_t ses_at = at;
-    if (nsessions)
+    if (nsessions && !resident)
         std::memcpy(stage + at, sessions, 8 * ses_u);
     else
         std::memset(stage + at, 0, 8 * ses_u);
@@ -357,17 +371,19 @@ int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, co
     const size_t extra_at = at;
     if (lg) {
         std::memset(stage + at, 0, 8 * extra_u);
-        uint32_t* acc = reinterpret_cast<uint32_t*>(stage + at);
-        uint64_t* wgt = stage + at + LedgerStage::acc_units(ses_staged);
-        for (size_t s = 0; s < nsessions; ++s) acc[s] = lg->accounts ? lg->accounts[s] : (uint32_t)s;
-        for (size_t s = 0; s < nsessions; ++s) wgt[s] = lg->weights ? lg->weights[s] : 1ull;
+        if (!resident) {
+            uint32_t* acc = reinterpret_cast<uint32_t*>(stage + at);
+            uint64_t* wgt = stage + at + LedgerStage::acc_units(ses_staged);
+            for (size_t s = 0; s < nsessions; ++s) acc[s] = lg->accounts ? lg->accounts[s] : (uint32_t)s;
+            for (size_t s = 0; s < nsessions; ++s) wgt[s] = lg->weights ? lg->weights[s] : 1ull;
+        }
         at += extra_u;
     }
     if (ctl_u) std::memset(stage + at, 0, 8 * ctl_u);
     BM_HIP(hipMemcpyAsync(d.d_verify, stage, 8 * in_u, hipMemcpyHostToDevice, d.stream));
     const JobsVerifyDesc* d_desc = reinterpret_cast<const JobsVerifyDesc*>(d.d_verify + desc_at);
     const uint32_t* d_words = reinterpret_cast<const uint32_t*>(d.d_verify + words_at);
-    const uint32_t* d_ses = reinterpret_cast<const uint32_t*>(d.d_verify + ses_at);
+    const uint32_t* d_ses = resident ? lg->d_sessions : reinterpret_cast<const uint32_t*>(d.d_verify + ses_at);
     uint32_t nses = (uint32_t)nsessions;
     const bm_jobs_submit_t* d_sub = reinterpret_cast<const bm_jobs_submit_t*>(d.d_verify + sub_at);
     const JobsVerifyBlock* d_blk = reinterpret_cast<const JobsVerifyBlock*>(d.d_verify + blk_at);
@@ -382,6 +398,15 @@ int jobs_verify_launch(DeviceCtx& d, const bm_pool_job_t* jobs, size_t njobs, co
     st.got = reinterpret_cast<const bm_job_verdict_t*>(d.h_verify + in_u);
     st.d_sub = d_sub;
     st.extra_at = extra_at;
+    if (resident) {
+        st.d_acc = lg->d_accounts;
+        st.d_wgt = lg->d_weights;
+        st.ctl_at = extra_at;
+    } else if (lg) {
+        st.d_acc = reinterpret_cast<const uint32_t*>(d.d_verify + extra_at);
+        st.d_wgt = d.d_verify + extra_at + LedgerStage::acc_units(ses_staged);
+        st.ctl_at = extra_at + LedgerStage::acc_units(ses_staged) + ses_staged;
+    }
     *staged = h_staged;
     return BM_OK;
 }
@@ -612,9 +637,7 @@ int ledger_fill(DeviceCtx& d, bm_ledger_t* ledger, size_t first, size_t count) {
 // and the final verdicts on the device, its seven control words back, and their
 // compare with the totals of the verdicts the host holds (`want`).  From the launch
 // on the rows may hold a part of this call: a failure poisons the ledger.
-int ledger_credit(bm_ledger_t* ledger, DeviceCtx& d, const PoolStage& st, size_t n, size_t nsessions,
-                  const host::LedgerTotals& want) {
-    const size_t ses_staged = nsessions ? nsessions : 1;
+int ledger_credit_launch(bm_ledger_t* ledger, DeviceCtx& d, const PoolStage& st, size_t n, size_t nsessions) {
     LedgerArgs A;
     A.n = (uint32_t)n;
     A.nsessions = (uint32_t)nsessions;
@@ -622,15 +645,22 @@ int ledger_credit(bm_ledger_t* ledger, DeviceCtx& d, const PoolStage& st, size_t
     A.rounds = ledger->peel;
     const uint32_t* d_sub = reinterpret_cast<const uint32_t*>(st.d_sub);
     const uint32_t* d_verdicts = st.d_out;
-    const uint32_t* d_acc = reinterpret_cast<const uint32_t*>(d.d_verify + st.extra_at);
-    const uint64_t* d_wgt = d.d_verify + st.extra_at + LedgerStage::acc_units(ses_staged);
-    const size_t ctl_at = st.extra_at + LedgerStage::acc_units(ses_staged) + ses_staged;
-    uint64_t* d_ctl = d.d_verify + ctl_at;
+    const uint32_t* d_acc = st.d_acc;
+    const uint64_t* d_wgt = st.d_wgt;
+    uint64_t* d_ctl = d.d_verify + st.ctl_at;
     uint64_t* d_rows = ledger->d_rows;
     void* args[] = {&A, &d_sub, &d_verdicts, &d_acc, &d_wgt, &d_rows, &d_ctl};
     ledger->poisoned = true;
     BM_HIP(hipLaunchKernel(g_ledger_credit, dim3((uint32_t)((n + kLedgerThreads - 1) / kLedgerThreads)),
                            dim3(kLedgerThreads), args, 0, d.stream));
+    return BM_OK;
+}
+
+int ledger_credit(bm_ledger_t* ledger, DeviceCtx& d, const PoolStage& st, size_t n, size_t nsessions,
+                  const host::LedgerTotals& want) {
+    BM_TRY(ledger_credit_launch(ledger, d, st, n, nsessions));
+    const size_t ctl_at = st.ctl_at;
+    uint64_t* d_ctl = d.d_verify + ctl_at;
     BM_HIP(hipMemcpyAsync(d.h_verify + ctl_at, d_ctl, 8 * kLedgerCtlWords, hipMemcpyDeviceToHost, d.stream));
     BM_HIP(hipStreamSynchronize(d.stream));
     if (std::memcmp(d.h_verify + ctl_at, want.word, 8 * kLedgerCtlWords) != 0) return BM_EINTERNAL;
@@ -757,6 +787,285 @@ int ledger_create_impl(bm_ctx* ctx, bm_ledger_t* ledger) {
     return ledger_clear_op(ledger);
 }
 
+// ---- the session table on a device (bm_sessions_host.hpp, bm_sessions.hpp) ----
+// The three kernels, registered by bm_sessions_inst.hip at load time
+const void* g_sessions_set = nullptr;
+const void* g_sessions_tally = nullptr;
+const void* g_sessions_retarget = nullptr;
+
+// bm_sessions_set: the resolved records up in one copy, one launch scatters them.  The
+// buffers are job_verify_impl's.  From the launch on slots may hold a part of the call:
+// a failure poisons the table.
+int sessions_set_impl(bm_sessions_t* t, const SessionSetRecord* recs, size_t k, uint64_t now_ms) {
+    if (!g_sessions_set) return BM_EINTERNAL;
+    DeviceCtx& d = t->ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    const size_t units = k * sizeof(SessionSetRecord) / 8;
+    BM_TRY(grow(d, d.h_verify, d.hverify_cap, units, sizeof(uint64_t), true));
+    BM_TRY(grow(d, d.d_verify, d.verify_cap, units));
+    std::memcpy(d.h_verify, recs, 8 * units);
+    BM_HIP(hipMemcpyAsync(d.d_verify, d.h_verify, 8 * units, hipMemcpyHostToDevice, d.stream));
+    uint32_t n = (uint32_t)k, capacity = (uint32_t)t->capacity;
+    const uint32_t* d_recs = reinterpret_cast<const uint32_t*>(d.d_verify);
+    void* args[] = {&n, &capacity, &now_ms, &d_recs, &t->d_sessions, &t->d_accounts, &t->d_weights, &t->d_state};
+    t->poisoned = true;
+    BM_HIP(hipLaunchKernel(g_sessions_set, dim3((n + kSessionsThreads - 1) / kSessionsThreads), dim3(kSessionsThreads),
+                           args, 0, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    t->poisoned = false;
+    return BM_OK;
+}
+
+int sessions_set_op(bm_sessions_t* t, const SessionSetRecord* recs, size_t k, uint64_t now_ms) {
+    DeviceGuard guard;
+    return guarded([&] { return sessions_set_impl(t, recs, k, now_ms); });
+}
+
+// The states of slots [first, first + count): one copy down on the stream.
+int sessions_states_op(bm_sessions_t* t, size_t first, size_t count, bm_session_state_t* out) {
+    DeviceGuard guard;
+    DeviceCtx& d = t->ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    BM_HIP(hipMemcpyAsync(out, t->d_state + kSessionStateWords * first, count * sizeof(bm_session_state_t),
+                          hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    return BM_OK;
+}
+
+// What follows a verified batch once the call can no longer be refused: the credit
+// kernel with a ledger, the tally kernel, the eight control words back in one copy and
+// their compare with the totals of the verdicts the host holds.  From the first launch
+// on the rows and the states may hold a part of this call: a failure poisons both.
+int sessions_after(bm_sessions_t* t, bm_ledger_t* ledger, DeviceCtx& d, const PoolStage& st, size_t n, size_t nsessions,
+                   const host::LedgerTotals& want) {
+    if (ledger) BM_TRY(ledger_credit_launch(ledger, d, st, n, nsessions));
+    SessionsTallyArgs A;
+    A.n = (uint32_t)n;
+    A.nsessions = (uint32_t)nsessions;
+    const uint32_t* d_sub = reinterpret_cast<const uint32_t*>(st.d_sub);
+    const uint32_t* d_verdicts = st.d_out;
+    uint64_t* d_state = t->d_state;
+    uint64_t* d_ctl = d.d_verify + st.ctl_at;
+    uint64_t* d_tally = d_ctl + kTallyCtlWord;
+    void* args[] = {&A, &d_sub, &d_verdicts, &d_state, &d_tally};
+    t->poisoned = true;
+    BM_HIP(hipLaunchKernel(g_sessions_tally, dim3((uint32_t)((n + kSessionsThreads - 1) / kSessionsThreads)),
+                           dim3(kSessionsThreads), args, 0, d.stream));
+    static_assert(kTallyCtlWord < kLedgerCtlUnits && kTallyCtlWord >= kLedgerCtlWords, "the tally's word is the padding");
+    BM_HIP(hipMemcpyAsync(d.h_verify + st.ctl_at, d_ctl, 8 * kLedgerCtlUnits, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    const uint64_t* got = d.h_verify + st.ctl_at;
+    if (ledger) {
+        if (std::memcmp(got, want.word, 8 * kLedgerCtlWords) != 0) return BM_EINTERNAL;
+        ledger->poisoned = false;
+    }
+    if (got[kTallyCtlWord] != want.word[kLedgerAccepted]) return BM_EINTERNAL;
+    t->poisoned = false;
+    return BM_OK;
+}
+
+// bm_sessions_verify_jobs on a device table: ledger_verify_jobs_impl's two shapes over
+// the table's mirror on the host and the table's arrays on the device, with
+// sessions_after where the credit is.  The caller's arrays are written last.
+int sessions_verify_jobs_impl(bm_sessions_t* t, bm_ledger_t* ledger, bm_share_set_t* set, const bm_pool_job_t* jobs,
+                              size_t njobs, const bm_jobs_submit_t* submits, size_t n, bm_job_verdict_t* verdicts,
+                              bm_ledger_result_t* out) {
+    if (!g_sessions_tally || !g_jobs_verify || (ledger && !g_ledger_credit)) return BM_EINTERNAL;
+    if (ledger && ledger->poisoned) return BM_EINTERNAL;
+    const bm_pool_session_t* sessions = t->sessions.data();
+    const size_t nsessions = (size_t)t->count;
+    const uint64_t* weights = t->weights.data();
+    const LedgerStage lg = {t->accounts.data(), weights, t->d_sessions, t->d_accounts, t->d_weights};
+    host::JobsPlan plan;
+    const bm_jobs_submit_t* staged = nullptr;
+    host::LedgerTotals tot;
+    bm_share_set_result_t r;
+    if (set) {
+        BM_TRY(share_set_verify_impl(
+            set, n,
+            [&](DeviceCtx& d, PoolStage& st) {
+                return jobs_verify_launch(d, jobs, njobs, sessions, nsessions, submits, n, 1, n, st, plan, &staged, &lg);
+            },
+            [&](const bm_job_verdict_t* got) {
+                return host::jobs_verify_tripwire(jobs, njobs, sessions, nsessions, submits, n, plan, staged, got,
+                                                  BM_SUBMIT_DUPLICATE);
+            },
+            [&](DeviceCtx& d, const PoolStage& st) {
+                host::ledger_totals(submits, st.got, n, nsessions, weights, tot);
+                return sessions_after(t, ledger, d, st, n, nsessions, tot);
+            },
+            verdicts, &r));
+    } else {
+        DeviceCtx& d = t->ctx->devs[0];
+        BM_HIP(hipSetDevice(d.id));
+        PoolStage st;
+        BM_TRY(jobs_verify_launch(d, jobs, njobs, sessions, nsessions, submits, n, 0, 0, st, plan, &staged, &lg));
+        BM_HIP(hipMemcpyAsync(d.h_verify + st.in_u, st.d_out, 8 * st.out_u, hipMemcpyDeviceToHost, d.stream));
+        BM_HIP(hipStreamSynchronize(d.stream));
+        BM_TRY(host::jobs_verify_tripwire(jobs, njobs, sessions, nsessions, submits, n, plan, staged, st.got, 0));
+        host::ledger_totals(submits, st.got, n, nsessions, weights, tot);
+        BM_TRY(sessions_after(t, ledger, d, st, n, nsessions, tot));
+        host::share_set_count(st.got, n, r);
+        std::memcpy(verdicts, st.got, n * sizeof(bm_job_verdict_t));
+    }
+    host::ledger_result(r, tot, *out);
+    return BM_OK;
+}
+
+int sessions_verify_jobs_op(bm_sessions_t* t, bm_ledger_t* ledger, bm_share_set_t* set, const bm_pool_job_t* jobs,
+                            size_t njobs, const bm_jobs_submit_t* submits, size_t n, bm_job_verdict_t* verdicts,
+                            bm_ledger_result_t* out) {
+    DeviceGuard guard;
+    return guarded([&] { return sessions_verify_jobs_impl(t, ledger, set, jobs, njobs, submits, n, verdicts, out); });
+}
+
+// bm_sessions_retarget on a device table.  Device buffer, in 8-byte units: the eight
+// control words, then the change list of A.cap entries.  The decide pass, the control
+// words back, then exactly the entries the pass wrote; the host sorts them by session and
+// checks each against its mirror and against bm_target_from_difficulty_fx; then the apply
+// pass and the control words again.  Nothing is written to the table before the apply
+// pass: BM_EFULL leaves it as it was.
+// The compacted list (a wave's entries ascending, the waves in the order their atomics
+// landed) into `out`, ascending by session.  A short list is copied and sorted; a long
+// one goes through a table of positions by session, one pass over the slots.  An entry
+// whose session is out of range or repeated stays out of order: the caller's check fails.
+void sessions_order_changes(const bm_vardiff_change_t* list, size_t k, uint32_t count, bm_vardiff_change_t* out) {
+    if (k * 16 < count) {
+        std::memcpy(out, list, k * sizeof(bm_vardiff_change_t));
+        std::sort(out, out + k, [](const bm_vardiff_change_t& a, const bm_vardiff_change_t& b) { return a.session < b.session; });
+        return;
+    }
+    std::vector<uint32_t> at(count, 0xFFFFFFFFu);
+    size_t placed = 0;
+    for (size_t i = 0; i < k; ++i)
+        if (list[i].session < count && at[list[i].session] == 0xFFFFFFFFu) at[list[i].session] = (uint32_t)i;
+    for (uint32_t s = 0; s < count; ++s)
+        if (at[s] != 0xFFFFFFFFu) out[placed++] = list[at[s]];
+    for (size_t i = 0; placed < k; ++i)  // what found no place of its own: in the list's order, behind the rest
+        if (!(list[i].session < count && at[list[i].session] == (uint32_t)i)) out[placed++] = list[i];
+}
+
+int sessions_retarget_impl(bm_sessions_t* t, const SessionsRetargetArgs& args_in, bm_vardiff_change_t* changes,
+                           bm_vardiff_result_t* out) {
+    if (!g_sessions_retarget) return BM_EINTERNAL;
+    bm_vardiff_result_t r;
+    std::memset(&r, 0, sizeof r);
+    SessionsRetargetArgs A = args_in;
+    if (A.count == 0) {
+        *out = r;
+        return BM_OK;
+    }
+    DeviceCtx& d = t->ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    const size_t entry_u = sizeof(bm_vardiff_change_t) / 8;
+    const size_t units = kRetargetCtlWords + (size_t)A.cap * entry_u;
+    BM_TRY(grow(d, d.h_verify, d.hverify_cap, units, sizeof(uint64_t), true));
+    BM_TRY(grow(d, d.d_verify, d.verify_cap, units));
+    uint64_t* d_ctl = d.d_verify;
+    uint32_t* d_list = reinterpret_cast<uint32_t*>(d.d_verify + kRetargetCtlWords);
+    const dim3 grid((A.count + kSessionsThreads - 1) / kSessionsThreads), block(kSessionsThreads);
+    void* args[] = {&A, &t->d_sessions, &t->d_weights, &t->d_state, &d_list, &d_ctl};
+    BM_HIP(hipMemsetAsync(d_ctl, 0, 8 * kRetargetCtlWords, d.stream));
+    A.apply = 0;
+    BM_HIP(hipLaunchKernel(g_sessions_retarget, grid, block, args, 0, d.stream));
+    BM_HIP(hipMemcpyAsync(d.h_verify, d_ctl, 8 * kRetargetCtlWords, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    const uint64_t* ctl = d.h_verify;
+    r.open = ctl[kRetargetOpen], r.evaluated = ctl[kRetargetEvaluated], r.changed = ctl[kRetargetChanged];
+    r.raised = ctl[kRetargetRaised], r.lowered = ctl[kRetargetLowered];
+    if (r.open > A.count || r.evaluated > r.open || r.changed > r.evaluated || r.raised + r.lowered != r.changed) {
+        t->poisoned = true;
+        return BM_EINTERNAL;
+    }
+    if (r.changed > A.cap) {  // A.cap is the caller's, or the count where that is smaller
+        *out = r;
+        return BM_EFULL;
+    }
+    const size_t k = (size_t)r.changed;
+    if (k) {
+        BM_HIP(hipMemcpyAsync(d.h_verify + kRetargetCtlWords, d_list, k * sizeof(bm_vardiff_change_t),
+                              hipMemcpyDeviceToHost, d.stream));
+        BM_HIP(hipStreamSynchronize(d.stream));
+        sessions_order_changes(reinterpret_cast<const bm_vardiff_change_t*>(d.h_verify + kRetargetCtlWords), k, A.count,
+                               changes);
+    }
+    for (size_t i = 0; i < k; ++i) {
+        const bm_vardiff_change_t& c = changes[i];
+        uint8_t want[32];
+        bool ok = c.session < A.count && c.reserved == 0 && (i == 0 || changes[i - 1].session < c.session);
+        ok = ok && c.old_fx == t->weights[c.session] && c.new_fx != c.old_fx && c.new_fx != 0;
+        ok = ok && bm_target_from_difficulty_fx(c.new_fx, want) == BM_OK && std::memcmp(want, c.target, 32) == 0;
+        if (!ok) {
+            t->poisoned = true;
+            return BM_EINTERNAL;
+        }
+    }
+    A.apply = 1;
+    t->poisoned = true;
+    BM_HIP(hipLaunchKernel(g_sessions_retarget, grid, block, args, 0, d.stream));
+    BM_HIP(hipMemcpyAsync(d.h_verify, d_ctl, 8 * kRetargetCtlWords, hipMemcpyDeviceToHost, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    if (ctl[kRetargetApplied] != r.changed || ctl[kRetargetChanged] != r.changed) return BM_EINTERNAL;
+    t->poisoned = false;
+    *out = r;
+    return BM_OK;
+}
+
+int sessions_retarget_op(bm_sessions_t* t, const SessionsRetargetArgs& A, bm_vardiff_change_t* changes, size_t,
+                         bm_vardiff_result_t* out) {
+    DeviceGuard guard;
+    return guarded([&] { return sessions_retarget_impl(t, A, changes, out); });
+}
+
+// Every slot never set: zeros in all four arrays.
+int sessions_clear_op(bm_sessions_t* t) {
+    DeviceGuard guard;
+    DeviceCtx& d = t->ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    BM_HIP(hipMemsetAsync(t->d_sessions, 0, sizeof(bm_pool_session_t) * t->capacity, d.stream));
+    BM_HIP(hipMemsetAsync(t->d_accounts, 0, sizeof(uint32_t) * t->capacity, d.stream));
+    BM_HIP(hipMemsetAsync(t->d_weights, 0, sizeof(uint64_t) * t->capacity, d.stream));
+    BM_HIP(hipMemsetAsync(t->d_state, 0, sizeof(bm_session_state_t) * t->capacity, d.stream));
+    BM_HIP(hipStreamSynchronize(d.stream));
+    return BM_OK;
+}
+
+void sessions_destroy_op(bm_sessions_t* t) {
+    DeviceGuard guard;
+    DeviceCtx& d = t->ctx->devs[0];
+    (void)hipSetDevice(d.id);
+    (void)hipStreamSynchronize(d.stream);
+    if (t->d_sessions) (void)hipFree(t->d_sessions);
+    if (t->d_accounts) (void)hipFree(t->d_accounts);
+    if (t->d_weights) (void)hipFree(t->d_weights);
+    if (t->d_state) (void)hipFree(t->d_state);
+    t->d_sessions = t->d_accounts = nullptr;
+    t->d_weights = t->d_state = nullptr;
+}
+
+const SessionsDeviceOps kSessionsOps = {sessions_set_op,      sessions_states_op, sessions_verify_jobs_op,
+                                        sessions_retarget_op, sessions_clear_op,  sessions_destroy_op};
+
+// The table's four device arrays, every slot never set.  A failed allocation leaves what
+// it made to bm_sessions_destroy and the context as it was.
+int sessions_create_impl(bm_ctx* ctx, bm_sessions_t* t) {
+    DeviceCtx& d = ctx->devs[0];
+    BM_HIP(hipSetDevice(d.id));
+    const size_t bytes[4] = {sizeof(bm_pool_session_t), sizeof(uint32_t), sizeof(uint64_t), sizeof(bm_session_state_t)};
+    void* p[4] = {};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipMalloc(&p[i], bytes[i] * t->capacity);
+    t->d_sessions = static_cast<uint32_t*>(p[0]);
+    t->d_accounts = static_cast<uint32_t*>(p[1]);
+    t->d_weights = static_cast<uint64_t*>(p[2]);
+    t->d_state = static_cast<uint64_t*>(p[3]);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? BM_ENOMEM : BM_EHIP;
+    }
+    return sessions_clear_op(t);
+}
+
 }  // namespace
 }  // namespace bm
 
@@ -846,6 +1155,42 @@ int bm_ledger_create(bm_ctx_t* ctx, size_t rows, bm_ledger_t** out) {
     }
     *out = ledger;
     return BM_OK;
+}
+
+void bm_register_sessions_kernels(const void* set, const void* tally, const void* retarget) {
+    bm::g_sessions_set = set;
+    bm::g_sessions_tally = tally;
+    bm::g_sessions_retarget = retarget;
+}
+
+int bm_sessions_create(bm_ctx_t* ctx, size_t capacity, bm_sessions_t** out) {
+    if (!ctx || !out || capacity == 0 || capacity > BM_MAX_POOL_SESSIONS) return BM_EINVAL;
+    if (ctx->rank_ctx && ctx->world > 1) return BM_EINVAL;  // rank groups are out of scope
+    return bm::guarded([&] {
+        bm_sessions_t* t = new (std::nothrow) bm_sessions;
+        if (!t) return (int)BM_ENOMEM;
+        t->capacity = capacity;
+        t->ctx = ctx;
+        t->ops = &bm::kSessionsOps;
+        int rc = BM_OK;
+        try {  // the mirror
+            t->sessions.assign(capacity, bm_pool_session_t());
+            t->accounts.assign(capacity, 0);
+            t->weights.assign(capacity, 0);
+        } catch (...) {
+            rc = BM_ENOMEM;
+        }
+        if (rc == BM_OK) {
+            bm::DeviceGuard guard;
+            rc = bm::sessions_create_impl(ctx, t);
+        }
+        if (rc != BM_OK) {
+            bm_sessions_destroy(t);
+            return rc;
+        }
+        *out = t;
+        return (int)BM_OK;
+    });
 }
 
 void bm_register_job_verify_kernel(const void* fn) { bm::g_job_verify = fn; }

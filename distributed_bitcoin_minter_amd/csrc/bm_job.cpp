@@ -1,6 +1,6 @@
 // bm_job.cpp -- the pure-CPU entries of the Stratum job layer (include/btcminer.h):
 // bm_job_prevhash_from_stratum, bm_job_header, bm_job_verify_cpu,
-// bm_pool_verify_cpu, bm_jobs_verify_cpu, bm_target_from_difficulty.  They need no context and no GPU;
+// bm_pool_verify_cpu, bm_jobs_verify_cpu, bm_target_from_difficulty, bm_target_from_difficulty_fx.  They need no context and no GPU;
 // bm_search_job_shares_gpu (bm_search.cpp) builds its headers and
 // bm_job_verify_gpu and bm_pool_verify_gpu (bm_aux.hip) check their device with the same code
 // (bm_job.hpp).  Plain C++: no HIP in here.
@@ -108,6 +108,22 @@ int bm_target_from_difficulty(double difficulty, uint8_t target[32]) {
             }
     }
     if (saturate) std::memset(target, 0xFF, 32);
+    return BM_OK;
+}
+
+// target = floor(0xffff * 2^240 / difficulty_fx), the difficulty in units of 2^-32:
+// one long division of the four 64-bit words of the numerator by the 64-bit divisor.
+// The quotient is below 2^256 for every divisor >= 1: nothing saturates.
+int bm_target_from_difficulty_fx(uint64_t difficulty_fx, uint8_t target[32]) {
+    if (!target || difficulty_fx == 0) return BM_EINVAL;
+    const uint64_t num[4] = {0xffffull << 48, 0, 0, 0};      // most significant word first
+    unsigned __int128 rem = 0;
+    for (int i = 0; i < 4; ++i) {
+        rem = (rem << 64) | num[i];                           // rem < difficulty_fx before: below 2^128 here
+        const uint64_t q = (uint64_t)(rem / difficulty_fx);
+        rem -= (unsigned __int128)q * difficulty_fx;          // one 128-bit division per word, not two
+        for (int b = 0; b < 8; ++b) target[8 * i + b] = (uint8_t)(q >> (56 - 8 * b));
+    }
     return BM_OK;
 }
 

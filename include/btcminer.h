@@ -481,6 +481,11 @@ int bm_search_header_versions_hits_gpu(bm_ctx_t* ctx, const uint8_t header[80], 
  *   (one big-integer division, no floating point in the quotient), saturating at
  *   2^256 - 1; most significant byte first.  BM_EINVAL for a NaN, an infinity, a
  *   value <= 0 or a NULL target.
+ * bm_target_from_difficulty_fx: the same for a difficulty in units of 2^-32 (the unit
+ *   of the ledger's weights): target = floor(0xffff * 2^240 / difficulty_fx), exact
+ *   integer arithmetic; it never saturates (difficulty_fx = 1 gives 0xffff * 2^240).
+ *   Below 2^53 it is bm_target_from_difficulty(difficulty_fx / 2^32) byte for byte.
+ *   BM_EINVAL for 0 or a NULL target.
  *
  * bm_search_job_shares_gpu: for every extranonce2 of [en2_lo, en2_hi], ascending,
  * the header of (job, extranonce2, ntime) is scanned by the version-rolling share
@@ -554,6 +559,7 @@ typedef struct bm_job_shares_result {
 int bm_job_prevhash_from_stratum(const uint8_t in[32], uint8_t out[32]);
 int bm_job_header(const bm_job_t* job, uint64_t extranonce2, uint32_t ntime, uint32_t version, uint8_t header[80]);
 int bm_target_from_difficulty(double difficulty, uint8_t target[32]);
+int bm_target_from_difficulty_fx(uint64_t difficulty_fx, uint8_t target[32]);
 int bm_search_job_shares_gpu(bm_ctx_t* ctx, const bm_job_t* job, uint32_t ntime, uint64_t en2_lo, uint64_t en2_hi,
                              const uint32_t* versions, size_t nver, uint32_t nonce_lo, uint32_t nonce_hi,
                              const uint8_t target[32], bm_job_share_t* shares, size_t cap,
@@ -962,6 +968,134 @@ int bm_ledger_verify_jobs(bm_ledger_t* ledger, bm_share_set_t* set /* or NULL */
                           const uint32_t* accounts /* nsessions entries, or NULL */,
                           const uint64_t* weights /* nsessions entries, or NULL */, const bm_jobs_submit_t* submits,
                           size_t n, bm_job_verdict_t* verdicts, bm_ledger_result_t* out);
+
+/* ---- sessions: a device-resident session table with vardiff retargeting ---------------
+ * The sessions of a pool change slowly -- a connect, a disconnect, a retarget -- while
+ * submissions arrive all the time.  A bm_sessions_t is an opaque table of `capacity`
+ * slots that keeps what the pool calls take per session -- the bm_pool_session_t, the
+ * account and the weight -- and a bm_session_state_t per slot.  bm_sessions_create makes
+ * it on the first device of ctx, where it lives across calls as a share set and a ledger
+ * do, so that a verify call copies no session up; bm_sessions_create_cpu makes it in host
+ * memory, with no context: the specification.  Difficulty is a uint64_t in units of
+ * 2^-32 ("fx"), the unit of the ledger's weights; T(d) = bm_target_from_difficulty_fx(d).
+ *
+ * bm_sessions_set: slot index[j] (index == NULL: slot j) becomes the session
+ *   {init[j].extranonce1, target = T(difficulty_fx)} with account init[j].account and
+ *   weight difficulty_fx, its state {difficulty_fx, since_ms = now_ms, accepted = 0,
+ *   retargets = 0}.  difficulty_fx == 0 CLOSES the slot: target all zero (nothing is at
+ *   or below it), weight 0, never evaluated by a retarget.  `count` is 1 + the highest
+ *   index set since the last clear; a never-set slot below it is a closed slot with zero
+ *   extranonce1 and account 0.  An index that appears twice in one call: the later entry
+ *   wins.  All or nothing: an index >= capacity is BM_EINVAL and nothing changes.
+ * bm_sessions_get: slots [first, first + count) as the three arrays the pool calls take
+ *   and their states; any output may be NULL.  first + count may reach capacity (slots
+ *   past the table's count read as closed, never-set slots).
+ * bm_sessions_clear: count = 0, every slot never set; lifts poisoning (below).
+ * bm_sessions_count: the count and the capacity (either pointer may be NULL, not both).
+ *
+ * bm_sessions_verify_jobs is bm_ledger_verify_jobs over the table: with sessions,
+ *   accounts and weights as bm_sessions_get(0, count) returns them and nsessions = count,
+ *   `verdicts`, `out`, the ledger and the set end up byte for byte as bm_ledger_verify_jobs
+ *   leaves them; with ledger == NULL as if against a scratch ledger (no row anywhere
+ *   changes).  TALLY: every submission of ledger class accepted (rule 4 above) with
+ *   session < count also adds 1 to that slot's state.accepted.  All or nothing as
+ *   bm_ledger_verify_jobs: on any refusal the table, the ledger, the set, `verdicts` and
+ *   `out` are as before.  A failure after the tally's launch (a HIP error, or a control
+ *   word that does not match out->credited) POISONS the table until bm_sessions_clear:
+ *   every call on it but clear, count and destroy returns BM_EINTERNAL.
+ *   BM_EINVAL: everything bm_ledger_verify_jobs refuses; a CPU table with a device ledger
+ *   or set or the reverse; objects on another context; any account of a slot below count
+ *   >= the ledger's rows.
+ *
+ * bm_sessions_retarget applies one vardiff step at now_ms to every slot below count.  All
+ *   arithmetic is exact and unsigned; nothing is floating point.  For an OPEN slot
+ *   (difficulty_fx != 0) with state {old, since_ms, accepted, retargets}:
+ *     1. elapsed = now_ms >= since_ms ? now_ms - since_ms : 0.
+ *     2. The slot is EVALUATED when elapsed >= window_ms, or burst != 0 && accepted >= burst.
+ *     3. D = max(elapsed, 1), N = min(accepted, 2^32 - 1) * target_ms,
+ *        ideal = floor(old * N / D)                                  (a 128-bit product).
+ *     4. new = min(max(ideal, max(1, floor(old / max_down))), sat64(old * max_up)).
+ *     5. new is clamped to [min_difficulty_fx, max_difficulty_fx].
+ *     6. The slot is UNCHANGED when |new - old| * 1000 <= old * band_permille.
+ *     7. Every evaluated slot gets since_ms = now_ms, accepted = 0.
+ *     8. A changed slot also gets difficulty_fx = weight = new, target = T(new),
+ *        retargets += 1,
+ *     9. and yields one entry of `changes`, which is ascending by session.
+ *   *out counts the open, evaluated and changed slots, and the changed ones with new > old
+ *   (raised) and new < old (lowered).  changed > cap: BM_EFULL; *out still holds the exact
+ *   counts, `changes` is untouched and the table is exactly as before, windows and
+ *   counters included.  target_ms is 1..2^32-1, 1 <= min <= max, max_up and max_down >= 1,
+ *   band_permille <= 1000: BM_EINVAL otherwise, and for a NULL table, policy or out, or
+ *   NULL changes with cap != 0.
+ *   A retarget takes effect at the next verify call: shares of jobs sent before the
+ *   caller's mining.set_difficulty are judged at the new difficulty (real pools keep a
+ *   grace period), so a few above-target rejects may follow a raise.
+ *
+ * On the device the table is four arrays -- bm_pool_session_t[capacity], uint32_t
+ * accounts[capacity], uint64_t weights[capacity], the layouts jobs_verify_kernel and
+ * ledger_credit_kernel read, and the states -- and the host keeps a mirror of the first
+ * three (the verify tripwire and bm_sessions_get read it; states are read back).
+ * bm_sessions_set resolves repeated indices on the host and scatters the staged records
+ * (sessions_set_kernel: one lane per record, no two writers of a slot).  The verify call is
+ * bm_ledger_verify_jobs's with the table's arrays neither staged nor copied: the existing
+ * kernels get the table's pointers, and sessions_tally_kernel runs where
+ * ledger_credit_kernel runs, one lane per staged record, one no-return atomicAdd per
+ * accepted lane (vardiff itself keeps a session at a few shares per window) and one per
+ * wave into a control word that the host compares with out->credited.
+ * sessions_retarget_kernel takes one lane per slot below count and runs twice: a decide
+ * pass that only reads the table, counts, and compacts the changes into a list (only
+ * changed lanes run the 256-bit by 64-bit division), and, once the host has seen that the
+ * list fits and has recomputed every target in it (BM_EINTERNAL and a poisoned table on a
+ * difference), an apply pass that rewrites the slots.  The host sorts the list by session
+ * and applies it to its mirror.
+ *
+ * Calls on one table are serialized by the caller; a device table is destroyed before its
+ * context; bm_sessions_destroy(NULL) is fine.  Out of scope: the grace period above; the
+ * single-job and per-call-array entry points taking a table; tables over several devices
+ * or rank groups (BM_EINVAL); a network Stratum server; payout policy. */
+typedef struct bm_sessions bm_sessions_t;
+typedef struct bm_session_init {        /* 24 bytes */
+    uint8_t extranonce1[8];
+    uint64_t difficulty_fx;             /* 0: the slot is closed */
+    uint32_t account, reserved;
+} bm_session_init_t;
+typedef struct bm_session_state {       /* 32 bytes */
+    uint64_t difficulty_fx;             /* 0: closed */
+    uint64_t since_ms;                  /* start of the slot's window */
+    uint64_t accepted;                  /* accepted submissions since then */
+    uint64_t retargets;                 /* changes since the slot was set */
+} bm_session_state_t;
+typedef struct bm_vardiff_policy {      /* 48 bytes */
+    uint64_t target_ms;                 /* the time one share should take, 1..2^32-1 */
+    uint64_t window_ms;                 /* a slot is evaluated once its window is this long */
+    uint64_t min_difficulty_fx, max_difficulty_fx;
+    uint32_t burst;                     /* or once it has this many accepted shares; 0: off */
+    uint32_t band_permille;             /* a change within old * band / 1000 is none, 0..1000 */
+    uint32_t max_up, max_down;          /* one step multiplies by at most max_up, divides by at most max_down */
+} bm_vardiff_policy_t;
+typedef struct bm_vardiff_change {      /* 56 bytes */
+    uint32_t session, reserved;
+    uint64_t old_fx, new_fx;
+    uint8_t target[32];                 /* T(new_fx), most significant byte first */
+} bm_vardiff_change_t;
+typedef struct bm_vardiff_result {      /* 40 bytes */
+    uint64_t open, evaluated, changed, raised, lowered;
+} bm_vardiff_result_t;
+
+int bm_sessions_create(bm_ctx_t* ctx, size_t capacity, bm_sessions_t** out);   /* capacity 1..BM_MAX_POOL_SESSIONS */
+int bm_sessions_create_cpu(size_t capacity, bm_sessions_t** out);
+void bm_sessions_destroy(bm_sessions_t* table);
+int bm_sessions_clear(bm_sessions_t* table);
+int bm_sessions_count(const bm_sessions_t* table, uint64_t* count, uint64_t* capacity);
+int bm_sessions_set(bm_sessions_t* table, const uint32_t* index /* k entries, or NULL: 0..k-1 */, size_t k,
+                    const bm_session_init_t* init, uint64_t now_ms);
+int bm_sessions_get(bm_sessions_t* table, size_t first, size_t count, bm_pool_session_t* sessions,
+                    uint32_t* accounts, uint64_t* weights, bm_session_state_t* state);
+int bm_sessions_verify_jobs(bm_sessions_t* table, bm_ledger_t* ledger /* or NULL */, bm_share_set_t* set /* or NULL */,
+                            const bm_pool_job_t* jobs, size_t njobs, const bm_jobs_submit_t* submits, size_t n,
+                            bm_job_verdict_t* verdicts, bm_ledger_result_t* out);
+int bm_sessions_retarget(bm_sessions_t* table, uint64_t now_ms, const bm_vardiff_policy_t* policy,
+                         bm_vardiff_change_t* changes, size_t cap, bm_vardiff_result_t* out);
 
 /* Batched bitcoin.Hash (hash.go:11-15) on the first device of ctx:
  * out[i] = Hash(msg, nonces[i]) for i < n. */

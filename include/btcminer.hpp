@@ -552,6 +552,111 @@ class Ledger {
     bm_ledger_t* ledger_ = nullptr;
 };
 
+// floor(0xffff * 2^240 / difficulty_fx), the difficulty in units of 2^-32, as 32 bytes,
+// most significant first: bm_target_from_difficulty_fx
+inline void target_from_difficulty_fx(uint64_t difficulty_fx, uint8_t target[32]) {
+    check(bm_target_from_difficulty_fx(difficulty_fx, target), "bm_target_from_difficulty_fx");
+}
+
+// Owns a bm_sessions_t: the pool's sessions -- extranonce1, share target, account and
+// weight per slot -- and a bm_session_state_t per slot, kept across calls so that a
+// verify call copies no session, with the vardiff step on top.  On the first device of a
+// context (destroy it before the context), or SessionTable::cpu(capacity) in host memory
+// with no GPU: the specification.  Not thread-safe; a device table shares its context's
+// buffers, so one call at a time per context.
+class SessionTable {
+   public:
+    SessionTable(Context& ctx, size_t capacity) {
+        check(bm_sessions_create(ctx.get(), capacity, &table_), "bm_sessions_create");
+    }
+    static SessionTable cpu(size_t capacity) {
+        SessionTable t;
+        check(bm_sessions_create_cpu(capacity, &t.table_), "bm_sessions_create_cpu");
+        return t;
+    }
+    SessionTable(const SessionTable&) = delete;
+    SessionTable& operator=(const SessionTable&) = delete;
+    SessionTable(SessionTable&& o) noexcept : table_(o.table_) { o.table_ = nullptr; }
+    SessionTable& operator=(SessionTable&& o) noexcept {
+        if (this != &o) {
+            bm_sessions_destroy(table_);
+            table_ = o.table_;
+            o.table_ = nullptr;
+        }
+        return *this;
+    }
+    ~SessionTable() { bm_sessions_destroy(table_); }
+
+    // Slot index[j] (index == nullptr: slot j) becomes init[j] with a fresh state whose
+    // window starts at now_ms; difficulty_fx 0 closes the slot; a slot named twice takes
+    // its later entry: bm_sessions_set.
+    void set(const uint32_t* index, const std::vector<bm_session_init_t>& init, uint64_t now_ms) {
+        check(bm_sessions_set(table_, index, init.size(), init.empty() ? nullptr : init.data(), now_ms), "bm_sessions_set");
+    }
+    // Slots [first, first + count) as the arrays the pool calls take; any output may be nullptr.
+    void get(size_t first, size_t count, std::vector<bm_pool_session_t>* sessions, std::vector<uint32_t>* accounts,
+             std::vector<uint64_t>* weights, std::vector<bm_session_state_t>* state) {
+        std::vector<bm_pool_session_t> s(sessions ? count : 0);
+        std::vector<uint32_t> a(accounts ? count : 0);
+        std::vector<uint64_t> w(weights ? count : 0);
+        std::vector<bm_session_state_t> st(state ? count : 0);
+        check(bm_sessions_get(table_, first, count, s.empty() ? nullptr : s.data(), a.empty() ? nullptr : a.data(),
+                              w.empty() ? nullptr : w.data(), st.empty() ? nullptr : st.data()),
+              "bm_sessions_get");
+        if (sessions) *sessions = std::move(s);
+        if (accounts) *accounts = std::move(a);
+        if (weights) *weights = std::move(w);
+        if (state) *state = std::move(st);
+    }
+    std::vector<bm_session_state_t> state(size_t first, size_t count) {
+        std::vector<bm_session_state_t> st;
+        get(first, count, nullptr, nullptr, nullptr, &st);
+        return st;
+    }
+    // Ledger::verify_jobs over the table's sessions, accounts and weights (ledger ==
+    // nullptr: no row changes), and every accepted submission counts in its slot's
+    // state: bm_sessions_verify_jobs.  All or nothing, as Ledger::verify_jobs.
+    bm_ledger_result_t verify_jobs(Ledger* ledger, ShareSet* set, const std::vector<PoolJob>& jobs,
+                                   const bm_jobs_submit_t* submits, size_t n, std::vector<bm_job_verdict_t>& verdicts) {
+        const std::vector<bm_pool_job_t> j = pool_job_views(jobs, "SessionTable::verify_jobs");
+        bm_ledger_result_t r;
+        std::vector<bm_job_verdict_t> buf(n);
+        check(bm_sessions_verify_jobs(table_, ledger ? ledger->get() : nullptr, set ? set->get() : nullptr,
+                                      j.empty() ? nullptr : j.data(), j.size(), submits, n, n ? buf.data() : nullptr, &r),
+              "bm_sessions_verify_jobs");
+        verdicts = std::move(buf);
+        return r;
+    }
+    // One vardiff step at now_ms: bm_sessions_retarget.  `changes` gets the changed slots,
+    // ascending; room for `cap` of them (Error with status BM_EFULL, and the table as
+    // before, when more change).
+    bm_vardiff_result_t retarget(uint64_t now_ms, const bm_vardiff_policy_t& policy, size_t cap,
+                                 std::vector<bm_vardiff_change_t>& changes) {
+        bm_vardiff_result_t r;
+        std::vector<bm_vardiff_change_t> buf(cap);
+        check(bm_sessions_retarget(table_, now_ms, &policy, cap ? buf.data() : nullptr, cap, &r), "bm_sessions_retarget");
+        buf.resize((size_t)r.changed);
+        changes = std::move(buf);
+        return r;
+    }
+    void clear() { check(bm_sessions_clear(table_), "bm_sessions_clear"); }
+    uint64_t count() const {
+        uint64_t n = 0;
+        check(bm_sessions_count(table_, &n, nullptr), "bm_sessions_count");
+        return n;
+    }
+    uint64_t capacity() const {
+        uint64_t n = 0;
+        check(bm_sessions_count(table_, nullptr, &n), "bm_sessions_count");
+        return n;
+    }
+    bm_sessions_t* get() const { return table_; }
+
+   private:
+    SessionTable() = default;
+    bm_sessions_t* table_ = nullptr;
+};
+
 }  // namespace btcminer
 
 namespace bitcoin {
