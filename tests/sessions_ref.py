@@ -3,7 +3,24 @@ of bm_sessions_*: a pure-Python model -- big integers for the difficulty-to-targ
 function and the vardiff rule, tests/ledger_ref.Model (hashlib verdicts, a Python set,
 a dict of rows) for the verify call.  The library is never its own reference; where a
 scenario takes a `witness`, a CPU table runs beside a device table and every byte of
-the two must agree as well.  Every comparison is exact equality."""
+the two must agree as well.  Every comparison is exact equality.
+
+The CPU table computes the rule with a 128-bit type and the device table in the 64-bit
+words of bm_sessions_args.hpp, so the model is what judges both.  Two scenarios put
+that arithmetic and the change list where small numbers never take them:
+* wide_arithmetic: policies, difficulties, clocks and counts of every bit length up to
+  64, with directed rows (directed_rows()) on the division's saturation edge, the step
+  and range clamps, the band's edge with products above 2^64 and old * max_up around
+  2^64.  It pins the high partial products and carries of mul_64x64, both branches of
+  div_128by64 for divisors up to 2^64 - 1, the high words of le_128 and every clamp.
+  The model alone counts, per class of CLASSES, the evaluated slots it sends through
+  the rule and fails below 20 in any class;
+* dense_changes: waves whose 64 lanes all change, one changed or one unchanged lane at
+  a wave's first and last lane, a cap of zero, one short, and at a wave edge inside a
+  longer list, and lists of 18 and 19 entries from five waves, either side of the
+  host's switch between sorting the list and placing it by slot.
+tests/test_sessions_arith.py runs trace()'s rule and directed_rows() against the
+header itself, compiled for the host."""
 import copy
 import ctypes
 import random
@@ -201,6 +218,13 @@ class Rig:
         self.model.set(entries, now_ms, index)
         if self.other is not None:
             self.other.set(entries, now_ms, index)
+        self.same()
+
+    def clear(self):
+        self.table.clear()
+        self.model.clear()
+        if self.other is not None:
+            self.other.clear()
         self.same()
 
     def verify(self, jobs, subs):
@@ -456,6 +480,255 @@ def contention(make_table, make_set, witness=None, witness_set=None):
             want = rig.verify(jobs, [one] * 130)
             assert want[1][8] == (1 if with_set else 130) and want[1][5] == (129 if with_set else 0)
             assert rig.table.state(64, 1)[0].accepted == (1 if with_set else 130)
+
+
+def trace(p, now_ms, state):
+    """The rule's intermediate values for one evaluated slot, in big integers: what the
+    directed rows are found by and the coverage classes are read from.  `ideal` is the
+    true quotient, 2^64 or more where the table saturates it."""
+    old, since, accepted, _ = state
+    D = max(now_ms - since if now_ms >= since else 0, 1)
+    N = min(accepted, U32) * p["target_ms"]
+    lo, hi = max(1, old // p["max_down"]), min(old * p["max_up"], U64)
+    ideal = old * N // D
+    cut = min(max(ideal, lo), hi)
+    new = min(max(cut, p["min_difficulty_fx"]), p["max_difficulty_fx"])
+    held = abs(new - old) * 1000 <= old * p["band_permille"]
+    assert vardiff(dict(p, window_ms=0), now_ms, state) == (True, old if held else new)
+    return dict(old=old, N=N, D=D, P=old * N, lo=lo, hi=hi, ideal=ideal, cut=cut, new=new, held=held)
+
+
+CLASSES = ("both high words", "P.hi >= D", "0 < P.hi < D", "0 < P.hi < D, D >= 2^63", "inside [lo, hi]", "cut by lo",
+           "cut by hi", "cut by min", "cut by max", "old * max_up >= 2^64", "band product >= 2^64", "raised", "lowered",
+           "held by the band")
+
+
+def classes(p, t):
+    """The coverage classes of CLASSES an evaluated slot falls in, from its trace."""
+    p_hi = t["P"] >> 64
+    diff = abs(t["new"] - t["old"])
+    is_in = {"both high words": t["old"] >> 32 and t["N"] >> 32,
+             "P.hi >= D": p_hi >= t["D"],
+             "0 < P.hi < D": 0 < p_hi < t["D"],
+             "0 < P.hi < D, D >= 2^63": 0 < p_hi < t["D"] and t["D"] >> 63,
+             "inside [lo, hi]": t["lo"] < t["ideal"] < t["hi"],
+             "cut by lo": t["ideal"] < t["lo"],
+             "cut by hi": t["ideal"] > t["hi"],
+             "cut by min": t["cut"] < p["min_difficulty_fx"],
+             "cut by max": t["cut"] > p["max_difficulty_fx"],
+             "old * max_up >= 2^64": t["old"] * p["max_up"] >> 64,
+             "band product >= 2^64": diff * 1000 >> 64 or t["old"] * p["band_permille"] >> 64,
+             "raised": not t["held"] and t["new"] > t["old"],
+             "lowered": not t["held"] and t["new"] < t["old"],
+             "held by the band": t["held"] and diff != 0}
+    return [c for c in CLASSES if is_in[c]]
+
+
+def find(p, want, olds, accepteds, elapseds):
+    """The first (old, accepted, elapsed) of the grid whose trace `want` accepts: a
+    directed row computed by the model."""
+    for old in olds:
+        for accepted in accepteds:
+            for elapsed in elapseds:
+                if want(trace(p, elapsed, (old, 0, accepted, 0))):
+                    return old, accepted, elapsed
+    raise AssertionError("no such row in the grid")
+
+
+# The policies of the directed rows of wide_arithmetic, one per round from the first on.
+# 0: the division's and the band's edges; 1 and 2: old * max_up around 2^64 where 2^64
+# (2^62 * 4) and 2^64 + 1 (67280421310721 * 274177) factor; 3: a [min, max] in mid-range.
+DIRECTED = (dict(target_ms=990, window_ms=0, min_difficulty_fx=50, max_difficulty_fx=U64, burst=0, band_permille=100,
+                 max_up=3, max_down=5),
+            dict(target_ms=U32, window_ms=0, min_difficulty_fx=1, max_difficulty_fx=U64, burst=0, band_permille=0,
+                 max_up=4, max_down=2),
+            dict(target_ms=U32, window_ms=0, min_difficulty_fx=1, max_difficulty_fx=U64, burst=0, band_permille=0,
+                 max_up=274177, max_down=2),
+            dict(target_ms=U32, window_ms=0, min_difficulty_fx=10 ** 6, max_difficulty_fx=10 ** 12, burst=0,
+                 band_permille=0, max_up=2, max_down=2))
+
+
+def directed_rows(k):
+    """[(old, accepted, elapsed)] under DIRECTED[k], in the style of EDGES; each row's
+    claim is asserted on the model's trace."""
+    p, rows = DIRECTED[k], []
+
+    def row(old, accepted, elapsed, claim):
+        assert claim(trace(p, elapsed, (old, 0, accepted, 0))), (k, old, accepted, elapsed)
+        rows.append((old, accepted, elapsed))
+
+    if k == 0:
+        # P = 2^63 * 2 * 990 = 990 * 2^64: P.hi against D = 989, 990, 991
+        for e in (989, 990, 991):
+            row(1 << 63, 2, e, lambda t: (t["P"] >> 64) - t["D"] == 990 - e)
+        for delta in (-1, 0, 1):  # the ideal one below, on and one above each of lo, hi and min
+            rows.append(find(p, lambda t: t["ideal"] - t["lo"] == delta, range(5000, 5010), (1,), range(4900, 5000)))
+            rows.append(find(p, lambda t: t["ideal"] - t["hi"] == delta, range(100, 120), (1, 2), range(300, 700)))
+            rows.append(find(p, lambda t: t["lo"] < t["ideal"] < t["hi"] and t["ideal"] - p["min_difficulty_fx"] == delta,
+                             range(200, 240), (1,), range(3000, 5000)))
+        row(U64 - 1, 1, 990, lambda t: t["ideal"] == U64 - 1)  # one below max, then on it; (1 << 63, 2, 990) is one above
+        row(U64, 1, 990, lambda t: t["ideal"] == t["hi"] == U64)
+        # the band's edge with both products above 2^64: diff * 1000 == old * 100 lowered (ideal = 0.9 old) and
+        # raised (ideal = 1.1 old), and the nearest values on each side
+        q = 2 * 10 ** 17
+        row(10 * q, 1, 1100, lambda t: t["held"] and (t["old"] - t["new"]) * 1000 == t["old"] * 100 >= 1 << 64)
+        row(10 * q - 1, 1, 1100, lambda t: not t["held"] and (t["old"] - t["new"]) * 1000 - t["old"] * 100 == 100)
+        row(10 * q + 1, 1, 1100, lambda t: not t["held"] and (t["old"] - t["new"]) * 1000 - t["old"] * 100 == 900)
+        row(10 * q, 1, 900, lambda t: t["held"] and (t["new"] - t["old"]) * 1000 == t["old"] * 100 >= 1 << 64)
+        row(10 * q + 1, 1, 900, lambda t: t["held"] and t["old"] * 100 - (t["new"] - t["old"]) * 1000 == 100)
+        row(10 * q, 1, 899, lambda t: not t["held"] and t["new"] > t["old"])
+        for delta in (-1, 0, 1):  # old * 3 = 2^64 - 4, 2^64 - 1, 2^64 + 2
+            row(U64 // 3 + delta, 6, 1, lambda t: t["old"] * 3 == (1 << 64) - 1 + 3 * delta and t["new"] == t["hi"])
+    elif k == 1:
+        for delta in (-1, 0, 1):  # old * 4 = 2^64 - 4, 2^64, 2^64 + 4
+            row((1 << 62) + delta, 1, 0, lambda t: t["old"] * 4 == (1 << 64) + 4 * delta and t["new"] == t["hi"])
+    elif k == 2:
+        for delta in (-1, 0, 1):  # old * 274177 = 2^64 + 1 and 274177 either side
+            row(67280421310721 + delta, 1, 0,
+                lambda t: t["old"] * 274177 == (1 << 64) + 1 + 274177 * delta and t["new"] == t["hi"])
+    else:
+        for delta in (-1, 0, 1):  # elapsed = target_ms and one accepted: the ideal is old itself
+            row(p["min_difficulty_fx"] + delta, 1, U32, lambda t: t["ideal"] - p["min_difficulty_fx"] == delta)
+            row(p["max_difficulty_fx"] + delta, 1, U32, lambda t: t["ideal"] - p["max_difficulty_fx"] == delta)
+    return rows
+
+
+WIDE_ROUNDS, WIDE_SLOTS, WIDE_FLOOR = 48, 300, 20
+FORMS = ("zero", "one", "thousands", "wide", "top", "negative")
+
+
+def random_bits(rng, lo, hi):
+    """A value whose bit length is uniform in lo..hi."""
+    bits = rng.randrange(lo, hi + 1)
+    return (1 << (bits - 1)) | rng.getrandbits(bits - 1)
+
+
+def wide_round(rng, r):
+    """One round of wide_arithmetic as data: (policy, now_ms, [(entries, since_ms,
+    index)] -- one per set call --, submissions)."""
+    if r < len(DIRECTED):
+        p = dict(DIRECTED[r])
+    else:
+        factor = lambda: rng.choice((1, 2, 4, random_bits(rng, 1, 32), U32))
+        lo, hi = sorted((random_bits(rng, 1, 64), random_bits(rng, 1, 64)))
+        p = dict(target_ms=U32 if r % 4 == 1 else random_bits(rng, 1, 32), window_ms=0, burst=0,
+                 band_permille=rng.choice((0, 1, 100, 999, 1000)), max_up=factor(), max_down=factor(),
+                 min_difficulty_fx=lo if r % 2 else 1, max_difficulty_fx=hi if r % 2 else U64)
+        if r in (10, 25, 40):  # the burst side of the rule: no window ever ends
+            p.update(window_ms=U64, burst=rng.randrange(1, 7))
+    # five of the six forms of `elapsed`, one per set call; now_ms = 2^64 - 1 where none is negative
+    forms = [f for k, f in enumerate(FORMS) if k != r % len(FORMS)]
+    rng.shuffle(forms)
+    now_ms = U64 if "negative" not in forms else (3 << 62) + rng.getrandbits(61)
+    since = {"zero": now_ms, "one": now_ms - 1, "thousands": now_ms - rng.randrange(1000, 20000),
+             "wide": now_ms - random_bits(rng, 33, 63), "top": rng.randrange(1000),
+             "negative": min(U64, now_ms + random_bits(rng, 1, 40))}
+    # about one slot in ten is closed, and one at each wave edge, on the side that alternates with the round
+    edge = (63, 128, 191, 256) if r % 2 else (64, 127, 192, 255)
+    sets, accepted = [], {}
+    for g, form in enumerate(forms):
+        index = [s for s in range(WIDE_SLOTS) if (s + r) % len(forms) == g]
+        entries = []
+        for s in index:
+            old = 0 if s % 10 == r % 10 or s in edge else random_bits(rng, 1, 64)
+            # slot % 7 accepted submissions; a part of the slots of a high `old` get two or more (N can pass 2^32)
+            accepted[s] = max(s % 7, 2) if old >> 32 and s % 2 else s % 7
+            entries.append((rng.randbytes(8), old, s % 5))
+        sets.append((entries, since[form], index))
+    if r < len(DIRECTED):  # the directed rows, across the wave edge at 64: a set call per distinct `elapsed`
+        by_since = {}
+        for s, (old, k, elapsed) in enumerate(directed_rows(r), 64 - 9):
+            accepted[s] = k
+            by_since.setdefault(now_ms - elapsed, []).append((s, (rng.randbytes(8), old, s % 5)))
+        sets += [([e for _, e in rows], at, [s for s, _ in rows]) for at, rows in by_since.items()]
+    subs = [sub for s in range(WIDE_SLOTS) for sub in accepted_subs(rng, s, accepted[s])]
+    return p, now_ms, sets, subs
+
+
+def wide_arithmetic(make_table, witness=None):
+    """The vardiff rule at full width: 48 rounds on one table of 300 slots, each with a
+    policy, difficulties and clocks of random bit lengths up to 64 (target_ms up to
+    2^32 - 1, elapsed from 0 to above 2^63 and negative), about a tenth of the slots
+    closed around the wave edges, one verify and one retarget; the first rounds carry
+    the directed rows of directed_rows().  The model alone first runs every round and
+    counts the evaluated slots per class of CLASSES: fewer than 20 in any is a failure
+    of the scenario, before a table is looked at.  -> the counts."""
+    rng = random.Random(19)
+    jobs = (block_job(rng),)
+    rounds = [wide_round(rng, r) for r in range(WIDE_ROUNDS)]
+    model, cover = Model(WIDE_SLOTS), dict.fromkeys(CLASSES, 0)
+    for p, now_ms, sets, subs in rounds:
+        model.clear()
+        for entries, since_ms, index in sets:
+            model.set(entries, since_ms, index)
+        model.verify(jobs, subs)
+        for state in model.states:
+            if state[0] and vardiff(p, now_ms, state)[0]:
+                for c in classes(p, trace(p, now_ms, state)):
+                    cover[c] += 1
+        model.retarget(now_ms, p, WIDE_SLOTS)
+    assert all(n >= WIDE_FLOOR for n in cover.values()), cover
+    with Rig(make_table, WIDE_SLOTS, witness) as rig:
+        for p, now_ms, sets, subs in rounds:
+            rig.clear()
+            for entries, since_ms, index in sets:
+                rig.set_slots(entries, since_ms, index)
+            rig.verify(jobs, subs)
+            changes, counts = rig.retarget(now_ms, p, WIDE_SLOTS)
+            assert changes is not None and counts[0] == sum(1 for s in rig.model.states if s[0])
+    return cover
+
+
+def dense_changes(make_table, witness=None):
+    """Full waves of changed lanes and both orderings of the change list: 300 open slots,
+    window 0, band 0 and nothing accepted, so every slot with old >= 2 is lowered to
+    max(1, old / 4) and a slot with old = 1 is evaluated and unchanged."""
+    rng = random.Random(20)
+    n = WIDE_SLOTS
+    p = dict(POLICY, window_ms=0, band_permille=0)
+
+    def fill(rig, changed, now_ms):
+        """Every slot anew: its own difficulty (the slot's number in bits 2..11 of 12 to 64) where it is to change, else 1."""
+        olds = [(rng.getrandbits(rng.randrange(53)) << 12) | ((s + 1) << 2) | rng.getrandbits(2) if s in changed else 1
+                for s in range(n)]
+        rig.set_slots([(rng.randbytes(8), old, s % 3) for s, old in enumerate(olds)], now_ms)
+        return [(s, old, old // 4, target_fx(old // 4)) for s, old in enumerate(olds) if s in changed]
+
+    def full(rig, now_ms, cap, changed):
+        """BM_EFULL with the exact counts, and the table byte for byte as before (the Rig checks the canaries)."""
+        before = raw_bytes(rig.table)
+        assert rig.retarget(now_ms, p, cap) == (None, (n, n, changed, 0, changed))
+        assert raw_bytes(rig.table) == before
+
+    with Rig(make_table, n, witness) as rig:
+        # every lane of every wave changed: the cap one short, zero, at the first wave's edge; then the whole list
+        expect = fill(rig, set(range(n)), 0)
+        for cap in (n - 1, 0, 64):
+            full(rig, 1, cap, n)
+        assert rig.retarget(1, p, n) == (expect, (n, n, n, 0, n))
+        assert len({c[3] for c in expect}) == n
+        assert [s.as_tuple() for s in rig.table.state()] == [(c[2], 1, 0, 1) for c in expect]
+        # nothing changed: an empty list fits a cap of zero
+        fill(rig, set(), 2)
+        assert rig.retarget(3, p, 0) == ([], (n, n, 0, 0, 0))
+        # one changed lane among unchanged ones, at the end and at the start of a wave
+        for k, lane in enumerate((63, 0, 64)):
+            expect = fill(rig, {lane}, 4 + k)
+            full(rig, 10 + k, 0, 1)
+            assert rig.retarget(10 + k, p, 1) == (expect, (n, n, 1, 0, 1))
+        # and the complement: every lane changed but that one
+        for k, lane in enumerate((63, 0, 64)):
+            expect = fill(rig, set(range(n)) - {lane}, 20 + k)
+            full(rig, 30 + k, n - 2, n - 1)
+            assert rig.retarget(30 + k, p, n - 1) == (expect, (n, n, n - 1, 0, n - 1))
+        # the host's two orderings of a list from all five waves: 18 * 16 < 300 sorts, 19 * 16 >= 300 places by slot
+        spread = [0, 63, 64, 255, 256, 299, 5, 31, 62, 65, 100, 127, 128, 170, 191, 192, 230, 270, 290]
+        for k in (18, 19):
+            assert {s // 64 for s in spread[:k]} == set(range(5)) and len(set(spread[:k])) == k
+            expect = fill(rig, set(spread[:k]), 40 + k)
+            full(rig, 70 + k, k - 1, k)
+            assert rig.retarget(70 + k, p, k) == (expect, (n, n, k, 0, k))
+            assert [c[0] for c in expect] == sorted(spread[:k])
 
 
 def refusals(make_table, make_ledger, make_set, foreign_ledger=None, foreign_set=None):

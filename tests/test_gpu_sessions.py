@@ -6,7 +6,18 @@ table, and everything -- verdicts, results, ledger rows, set counts, the table's
 arrays, its states and the change lists -- is compared byte for byte.  The scenarios
 are the CPU table's (tests/test_sessions_abi.py); the shapes are small and chosen for
 the places the kernels can go wrong: capacity 300 (a partial last wave), slots on both
-sides of the wave edges, closed slots in between."""
+sides of the wave edges, closed slots in between.
+
+The device is the only place the rule runs in the 64-bit words of bm_sessions_args.hpp
+inside a table (the CPU table uses a 128-bit type), and the host rechecks only the
+target of a change, never its new difficulty.  So two scenarios aim at it:
+* wide_arithmetic pins the kernel's multiply, division, compare and clamps with
+  operands of every bit length up to 64 and directed rows at their edges, 48 rounds of
+  300 slots, each class of operand counted by the model beforehand;
+* dense_changes pins the change list: the rank of lane 63 under a full ballot, the
+  wave bases the returning atomic hands out over five waves, `at < cap` with the cap
+  at zero, one short and at a wave edge, BM_EFULL leaving every byte alone, and both
+  of the host's orderings (18 and 19 entries of 300)."""
 import random
 
 import pytest
@@ -32,10 +43,12 @@ def device_set(ctx):
 
 
 @pytest.mark.parametrize("scenario", [sref.division, sref.division_by_retarget, sref.set_semantics, sref.edge_cases,
-                                      sref.burst_and_clock], ids=lambda f: f.__name__)
+                                      sref.burst_and_clock, sref.wide_arithmetic, sref.dense_changes],
+                         ids=lambda f: f.__name__)
 def test_device_table(gpu_ctx, scenario):
     """The division through set and get and as a retarget's new difficulty, set's
-    semantics, and the retarget edge cases, BM_EFULL one entry short included."""
+    semantics, the retarget edge cases, BM_EFULL one entry short included, the rule at
+    full 64-bit width and the dense change lists."""
     scenario(device_table(gpu_ctx), witness=SessionTable.cpu)
 
 

@@ -1,7 +1,9 @@
 """The session table on the CPU (no GPU): bm_target_from_difficulty_fx and the CPU
 bm_sessions_t, the specification of a device table, against the pure-Python model of
 tests/sessions_ref.py -- big integers, hashlib, a Python set and a dict of rows --
-never against the library itself, but where a test says so."""
+never against the library itself, but where a test says so.  wide_arithmetic (the rule
+at full 64-bit width) and dense_changes (full and nearly full change lists) are the
+scenarios a device table runs too (tests/test_gpu_sessions.py)."""
 import ctypes
 import io
 import os
@@ -79,7 +81,8 @@ def test_creation_and_python_arguments():
 
 
 @pytest.mark.parametrize("scenario", [sref.division, sref.division_by_retarget, sref.set_semantics, sref.edge_cases,
-                                      sref.burst_and_clock], ids=lambda f: f.__name__)
+                                      sref.burst_and_clock, sref.wide_arithmetic, sref.dense_changes],
+                         ids=lambda f: f.__name__)
 def test_cpu_table(scenario):
     scenario(SessionTable.cpu)
 
